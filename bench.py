@@ -1,5 +1,13 @@
-"""Headline bench: top-tcp interval aggregation (BASELINE.json configs[1]), plus the other
-SURVEY.md §8(d) configs in the same run.
+"""Headline bench: top-tcp interval aggregation (BASELINE.json configs[1]); with `--full`, the
+other SURVEY.md §8(d) configs in the same run.
+
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline figure needs: it
+generates the input slices, warms up, times the K steps, writes the last step's outputs when
+`--dump-outputs DIR` is given, and prints the JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  Everything else below -- the other configs,
+the CPU baselines, the roofline figures (HIP events around the dominant kernel) and the post-run
+checks against the oracle -- runs only with `--full`; without it `--configs`, `--cpu-sample`,
+`--config-*` and `--no-check` have nothing to act on.
 
 One headline step = one `top tcp` interval over a resident batch of synthetic events:
   reset the device table (the per-interval map drain, tracer.go:154-171)
@@ -12,7 +20,7 @@ One headline step = one `top tcp` interval over a resident batch of synthetic ev
 Events are hash-partitioned across GPUs at ingest (each rank owns its own key universe),
 so per-GPU work is fixed as N grows ("scaling": "weak").
 
-The other configs (`--configs`, default c1,c3,c4,c5) run after the headline with their own
+The other configs (`--full`; `--configs`, default c1,c3,c4,c5) run after the headline with their own
 timed steps and land in the line's "configs" object, each with its roofline and (rank 0,
 N=1) CPU baselines.  At N>1 their collectives are inside the timed region: C3 all-reduces
 the histogram, C4 and C5 exchange partial groups by key owner (every rank holds a slice of
@@ -56,6 +64,7 @@ C4_NAMES, C4_WIDTHS, C4_CAP = ("src", "pkt", "peer", "port"), [4, 1, 4, 2], 11_0
 C5_KEYS, C5_ZIPF, C5_TOPK = 10_000_000, 1.05, 20
 C5_NAMES, C5_WIDTHS = ("inode", "dev", "pid", "tid", "op", "count"), [8, 4, 4, 4]
 C5_CAP = C5_KEYS + C5_KEYS // 4
+DUMP_BUDGET = 64 << 20         # --dump-outputs: bytes of array data in all
 
 
 def c5_aggs(A):
@@ -109,7 +118,16 @@ def parse(argv=None):
                         "igx_dist_* transport needs one GPU per rank and is then reported unavailable")
     p.add_argument("--launch-dry-run", action="store_true",
                    help="launcher self-test: each rank prints its RANK/WORLD_SIZE and exits, no GPU")
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the other configs (--configs), the CPU baselines (--cpu-sample), the "
+                        "roofline figures and the post-run checks against the oracle (--no-check skips those)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed headline step computed (its top-K rows "
+                        f"and its table) as DIR/<name>.npy, float32 / float64, at most {DUMP_BUDGET >> 20} MB in all")
+    a = p.parse_args(argv)
+    if not a.full:   # a plain run: the headline's setup, warmup and timed steps only
+        a.check, a.cpu_sample, a.configs = False, 0, ""
+    return a
 
 
 def n_batches(a, steps, event_bytes, n):
@@ -462,6 +480,35 @@ def copied_pred(A, col, dir_col):
     return p
 
 
+def dump_c2(a, ctx, tab, cand, Gn):
+    """--dump-outputs: what the last timed interval handed its caller, as float .npy files (every
+    value is an integer below 2^53, so float64 holds it exactly; bytes go out as float32):
+      topk_rows   (K, 96)  the packed top-K Stats rows, byte for byte (key | sent | recv | first)
+      topk_sent / topk_recv / topk_first  (K,)  the same rows' u64 fields
+      n_groups    (1,)     the interval's group count
+      table       (G, 3)   first index, sent, recv of every group of the table, ordered by first
+                           index (unique per group; the slot order depends on which wave claims a
+                           slot first) -- past the byte budget a fixed, seeded sample of those rows
+    At N > 1 rank 0 writes the global top-K and its own table."""
+    torch, E, H = ctx["torch"], ctx["E"], ctx["H"]
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    top = H.host(cand)
+    rows = H.host(table_rows(E, torch, tab, tab.fin))
+    first = u64_col(rows, 88)
+    order = np.argsort(first, kind="stable")
+    table = np.stack([first[order], u64_col(rows, 72)[order], u64_col(rows, 80)[order]], axis=1).astype(np.float64)
+    del rows
+    arrays = {"topk_rows": top.astype(np.float32), "topk_sent": u64_col(top, 72).astype(np.float64),
+              "topk_recv": u64_col(top, 80).astype(np.float64), "topk_first": u64_col(top, 88).astype(np.float64),
+              "n_groups": np.array([Gn], dtype=np.float64)}
+    fit = (DUMP_BUDGET - sum(v.nbytes for v in arrays.values())) // table[:1].nbytes if len(table) else 0
+    if len(table) > fit:
+        table = table[np.sort(np.random.default_rng(0xD0C2).choice(len(table), fit, replace=False))]
+    arrays["table"] = table
+    for name, v in arrays.items():
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), v)
+
+
 def run_c2(a, ctx):
     torch, E, H, A, D, T = ctx["torch"], ctx["E"], ctx["H"], ctx["A"], ctx["D"], ctx["timer"]
     rank, world = ctx["rank"], ctx["world"]
@@ -487,7 +534,7 @@ def run_c2(a, ctx):
         st["i"] += 1
         st["b"] = b
         tab.reset()
-        clk.on = record
+        clk.on = record and a.full
         with clk:
             tab.update(colsets[b], list(range(8)), N, bases[b], preds)
         tab.finalize(sync=False)                      # the group count stays on the device
@@ -504,11 +551,15 @@ def run_c2(a, ctx):
     Gn = tab.wait()                                   # the last interval's group count
     alg = N * EV_BYTES + Gn * GROUP_BYTES
     out = {"value": world * N * a.steps / dt, "ms_per_step": dt * 1000.0 / a.steps, "groups_per_gpu": Gn,
-           "batches": len(bases), "claims_per_interval": tab.info()["claims"],
-           "roofline": roofline(alg, clk.avg(), "k_groupby<ip_key_t>",
-                                f"{EV_BYTES} B/event x events + {GROUP_BYTES} B/group x groups", "c2",
-                                {"events": N, "keys": G, "zipf": a.zipf})}
-    out["roofline"]["hbm_pct_of_peak_whole_step"] = 100.0 * alg / (out["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+           "batches": len(bases), "claims_per_interval": tab.info()["claims"]}
+    if a.full:
+        out["roofline"] = roofline(alg, clk.avg(), "k_groupby<ip_key_t>",
+                                   f"{EV_BYTES} B/event x events + {GROUP_BYTES} B/group x groups", "c2",
+                                   {"events": N, "keys": G, "zipf": a.zipf})
+        out["roofline"]["hbm_pct_of_peak_whole_step"] = (100.0 * alg / (out["ms_per_step"] * 1e-3) / 1e9
+                                                         / HBM_PEAK_GBS)
+    if a.dump_outputs and rank == 0:
+        dump_c2(a, ctx, tab, st["cand"], Gn)
     if a.check:
         out["check"] = check_c2(a, ctx, tab, st["cand"], cdf_h, Gn, bases[st["b"]])
         if world > 1:   # every rank takes part; rank 0 records it
@@ -973,7 +1024,7 @@ def main():
                                 + ("igx_dist_* (RCCL, C ABI)" if transport == "igx" else
                                    "torch.distributed (nccl = RCCL)")) if world > 1 else "single GPU",
             },
-            "roofline": c2["roofline"],
+            "roofline": c2.get("roofline"),
             "cpu_baseline": c2.get("cpu_baseline"),
             "configs": configs,
             "library": os.path.relpath(igx._abi.LIB_PATH, ROOT),

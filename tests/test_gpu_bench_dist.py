@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_gloo_rehearsal():
     env = dict(os.environ, OMP_NUM_THREADS="4", IGX_DIST_TIMEOUT_MS="20000")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo",
            "--events", "4000000", "--keys", "100000", "--config-events", "3000000", "--steps", "3",
            "--warmup", "1", "--config-steps", "2", "--cpu-sample", "0", "--configs", "c3,c4,c5",
            "--input-gb", "4"]

@@ -162,7 +162,7 @@ def _bench_ctx(igx, torch):
 
 def test_bench_c2_async_intervals_match_oracle(igx, torch):
     bench, ctx = _bench_ctx(igx, torch)
-    a = bench.parse(["--steps", "5", "--warmup", "1", "--cpu-sample", "0"])
+    a = bench.parse(["--full", "--steps", "5", "--warmup", "1", "--cpu-sample", "0"])
     out = bench.run_c2(a, ctx)
     ck = out["check"]
     assert ck["groups_equal"] and ck["table_checksum_equal"] and ck["topk_equal"], ck
@@ -171,7 +171,7 @@ def test_bench_c2_async_intervals_match_oracle(igx, torch):
 
 def test_bench_c5_async_intervals_match_oracle(igx, torch):
     bench, ctx = _bench_ctx(igx, torch)
-    a = bench.parse(["--config-steps", "5", "--cpu-sample", "0"])
+    a = bench.parse(["--full", "--config-steps", "5", "--cpu-sample", "0"])
     out = bench.run_c5(a, ctx)
     ck = out["check"]
     assert ck["groups_equal"] and ck["table_checksum_equal"] and ck["topk_equal"], ck

@@ -10,7 +10,7 @@ for rep in $(seq 1 $REPS); do
   i=0
   for S in "${SETS[@]}"; do
     i=$((i+1))
-    timeout -k 10 300 env $S python3 bench.py --steps 20 --warmup 5 --cpu-sample 0 --configs $CFG > $O/run${i}_$rep.log 2>&1 || { echo "run $i ($S) failed rc=$?"; tail -5 $O/run${i}_$rep.log; exit 1; }
+    timeout -k 10 300 env $S python3 bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --configs $CFG > $O/run${i}_$rep.log 2>&1 || { echo "run $i ($S) failed rc=$?"; tail -5 $O/run${i}_$rep.log; exit 1; }
     python3 - "$S" $O/run${i}_$rep.log <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[2]) if l.startswith('{"metric"')][-1]

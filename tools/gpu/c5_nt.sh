@@ -8,7 +8,7 @@ timeout -k 10 400 python3 -u -m pytest -x -q --timeout 300 --timeout-method thre
     > $O/tests.log 2>&1 || { echo "tests failed rc=$?"; tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
 for rep in 1 2; do
-  timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --cpu-sample 0 --no-check --configs c5 > $O/bench_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_$rep.log; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --cpu-sample 0 --no-check --configs c5 > $O/bench_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_$rep.log; exit 1; }
   python3 - $O/bench_$rep.log <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

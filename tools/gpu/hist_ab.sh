@@ -11,7 +11,7 @@ tail -1 $O/tests.log
 for rep in 1 2 3; do
   for v in new base; do
     if [ $v = base ]; then L=$B; else L=; fi
-    IGX_LIB=$L timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --cpu-sample 0 --no-check --configs c3 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
+    IGX_LIB=$L timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 --cpu-sample 0 --no-check --configs c3 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
     python3 - $O/bench_${v}_$rep.log $v <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 T=$1; CFG=$2; shift 2
 O=gpurun_out/kt_$T
 rm -rf $O; mkdir -p $O
-timeout -k 10 300 env "$@" rocprofv3 --kernel-trace --stats -d $O -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --cpu-sample 0 --config-steps 3 --configs=$CFG > $O/log 2>&1 || { echo "trace failed rc=$?"; tail -5 $O/log; exit 1; }
+timeout -k 10 300 env "$@" rocprofv3 --kernel-trace --stats -d $O -o run --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --cpu-sample 0 --config-steps 3 --configs=$CFG > $O/log 2>&1 || { echo "trace failed rc=$?"; tail -5 $O/log; exit 1; }
 f=$(find $O -name '*kernel_stats.csv' | head -1)
 python3 - "$f" "$T" <<'PY'
 import csv, sys, re

@@ -13,7 +13,7 @@ tail -1 $O/tests.log
 for rep in 1 2 3; do
   for v in new base; do
     if [ $v = base ]; then L=$B; else L=; fi
-    IGX_LIB=$L timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --cpu-sample 0 --no-check --configs c5 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
+    IGX_LIB=$L timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --cpu-sample 0 --no-check --configs c5 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
     python3 - $O/bench_${v}_$rep.log $v <<'PY'
 import json, sys
 for l in open(sys.argv[1]):
@@ -23,7 +23,7 @@ for l in open(sys.argv[1]):
 PY
   done
 done | tee $O/ab.txt || exit 1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --cpu-sample 0 --no-check --configs c5 > $O/trace.log 2>&1 || { echo "trace failed"; tail $O/trace.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --cpu-sample 0 --no-check --configs c5 > $O/trace.log 2>&1 || { echo "trace failed"; tail $O/trace.log; exit 1; }
 find $O/trace -name '*kernel_stats.csv' -exec cp {} $O/kernel_stats.csv \;
 cut -d, -f1-4 $O/kernel_stats.csv | head -30 | grep -E "k_groupby<|slots|reset" || true
 echo OCCB_OK

@@ -11,7 +11,7 @@ tail -1 $O/tests.log
 for rep in 1 2; do
   for v in on off; do
     if [ $v = off ]; then P=0; else P=1; fi
-    IGX_GB_PERSIST=$P timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --cpu-sample 0 --configs c5 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
+    IGX_GB_PERSIST=$P timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --cpu-sample 0 --configs c5 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
     python3 - $O/bench_${v}_$rep.log $v <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

@@ -13,7 +13,7 @@ cat $O/emul.log
 for rep in 1 2; do
   for v in seed noseed; do
     if [ $v = noseed ]; then S=0; else S=1; fi
-    IGX_GB_SEED=$S timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --cpu-sample 0 --configs c5 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
+    IGX_GB_SEED=$S timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --configs c5 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
     python3 - $O/bench_${v}_$rep.log $v <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

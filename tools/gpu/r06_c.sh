@@ -12,7 +12,7 @@ for m in direct cached part; do
 done
 for L in 8 9 7 def; do
   if [ $L = def ]; then unset IGX_GB_LOADERS; else export IGX_GB_LOADERS=$L; fi
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-check --configs c5 > $O/bench_L$L.log 2>&1 || { echo "bench failed"; tail $O/bench_L$L.log; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --no-check --configs c5 > $O/bench_L$L.log 2>&1 || { echo "bench failed"; tail $O/bench_L$L.log; exit 1; }
   python3 - $O/bench_L$L.log $L <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

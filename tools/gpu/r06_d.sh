@@ -13,7 +13,7 @@ cat $O/filter_scale.json
 bash tools/gpu/r06_atomics.sh > $O/atomics.txt 2>&1 || { echo "atomics failed"; tail -20 $O/atomics.txt; exit 1; }
 grep -A1 "counters:" $O/atomics.txt | grep -v "^--" | cut -c1-2000
 grep -A1 "PMC per launch" $O/atomics.txt | grep -v "^--"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --cpu-sample 0 --configs c5 > $O/bench.log 2>&1 || { echo "bench failed"; tail $O/bench.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --configs c5 > $O/bench.log 2>&1 || { echo "bench failed"; tail $O/bench.log; exit 1; }
 find $O/trace -name '*kernel_stats.csv' -exec cp {} $O/kernel_stats.csv \;
 python3 - $O/bench.log <<'PY'
 import json, sys

@@ -13,7 +13,7 @@ grep -A1 "PMC per launch" $O/atomics.txt | grep -v "^--"
 for rep in 1 2 3; do
   for v in align noalign; do
     if [ $v = noalign ]; then export IGX_LIB=inspektor-gadget_amd/libigx_noalign.so; else unset IGX_LIB; fi
-    timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-check --configs c5 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
+    timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --no-check --configs c5 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
     python3 - $O/bench_${v}_$rep.log $v <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

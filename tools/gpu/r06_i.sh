@@ -7,7 +7,7 @@ timeout -k 10 1000 python3 -u -m pytest tests -x -v -m gpu --timeout 200 --timeo
 tail -1 $O/tests.log
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; tail $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 600 python3 bench.py > $O/bench.log 2>&1 || { echo "bench failed rc=$?"; tail $O/bench.log; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $O/bench.log 2>&1 || { echo "bench failed rc=$?"; tail $O/bench.log; exit 1; }
 grep -h '"metric"' $O/bench.log > $O/bench.json
 python3 - $O/bench.json <<'PY'
 import json, sys

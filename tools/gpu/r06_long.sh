@@ -3,7 +3,7 @@ set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/r06long
 rm -rf $O; mkdir -p $O
-timeout -k 10 900 python3 -u bench.py --steps 100 --warmup 10 --config-steps 100 > $O/bench.log 2>&1 || { echo "bench failed rc=$?"; tail $O/bench.log; exit 1; }
+timeout -k 10 900 python3 -u bench.py --full --steps 100 --warmup 10 --config-steps 100 > $O/bench.log 2>&1 || { echo "bench failed rc=$?"; tail $O/bench.log; exit 1; }
 grep -h '"metric"' $O/bench.log > $O/bench.json
 python3 - $O/bench.json <<'PY'
 import json, sys

@@ -12,7 +12,7 @@ tail -1 $O/tests.log
 for rep in 1 2; do
   for v in on off; do
     if [ $v = off ]; then P=0; else P=1; fi
-    IGX_GB_PERSIST=$P timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --cpu-sample 0 --configs c5 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
+    IGX_GB_PERSIST=$P timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --configs c5 > $O/bench_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/bench_${v}_$rep.log; exit 1; }
     python3 - $O/bench_${v}_$rep.log $v <<'PY'
 import json, sys
 for l in open(sys.argv[1]):
@@ -27,7 +27,7 @@ done | tee $O/ab.txt || exit 1
 timeout -k 10 300 python3 tools/emulate_rank8.py --out $O/emulated_rank8.json > $O/emul.log 2>&1 || { echo "emulate failed"; tail $O/emul.log; exit 1; }
 cat $O/emul.log
 
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --cpu-sample 0 --no-check --configs c5 > $O/trace.log 2>&1 || { echo "trace failed"; tail $O/trace.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --cpu-sample 0 --no-check --configs c5 > $O/trace.log 2>&1 || { echo "trace failed"; tail $O/trace.log; exit 1; }
 find $O/trace -name '*kernel_stats.csv' -exec cp {} $O/kernel_stats.csv \;
 cut -d, -f1-4 $O/kernel_stats.csv | head -40
 echo TRACE_OK

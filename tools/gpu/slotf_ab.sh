@@ -2,7 +2,7 @@ set -o pipefail
 O=gpurun_out/slotf; rm -rf $O; mkdir -p $O
 for rep in 1 2; do
   for v in 8 6 5; do
-    IGX_GB_SLOTF=$v timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --cpu-sample 0 --no-check --configs c5 > $O/b_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/b_${v}_$rep.log; exit 1; }
+    IGX_GB_SLOTF=$v timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --cpu-sample 0 --no-check --configs c5 > $O/b_${v}_$rep.log 2>&1 || { echo "bench failed"; tail $O/b_${v}_$rep.log; exit 1; }
     python3 - $O/b_${v}_$rep.log $v <<'PY'
 import json, sys
 for l in open(sys.argv[1]):
