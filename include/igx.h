@@ -367,6 +367,27 @@ int igx_groupby_wait(igx_table *t, uint64_t *n_groups);
  * nextStats builds (pkg/gadgets/top/tcp/tracer/tracer.go:186-219).  Call after
  * igx_groupby_finalize.  Asynchronous. */
 int igx_groupby_gather(igx_table *t, const uint32_t *idx, uint64_t k, uint8_t *out_rows);
+/* The two table steps of the cross-rank threshold top-K.  Both follow
+ * igx_groupby_finalize or _async of the interval (IGX_EINVAL after a later update or reset),
+ * read the table only, and are asynchronous.
+ * igx_groupby_select_ge: the interval's group slots whose aggregate `agg`, wrapped to its
+ * out_width as igx_groupby_gather wraps it, is >= threshold, in no particular order.  The group
+ * count is read on the device.  *d_count (device u64) receives how many qualify; the first cap
+ * of them go to out_slots (device u32, cap entries; nothing past cap is written, and d_count may
+ * exceed cap: the list is then incomplete). */
+int igx_groupby_select_ge(igx_table *t, uint32_t agg, uint64_t threshold, uint32_t *out_slots,
+                          uint64_t cap, uint64_t *d_count);
+/* igx_groupby_lookup: keys (device, 4-byte aligned) holds n packed keys in the table's key
+ * layout (key_bytes, each column padded to 4 with zeros), key_stride bytes apart (a multiple of
+ * 4) -- rows of igx_groupby_gather can be passed as they are.  For a key that is a group of the
+ * finalized interval, out_rows[i] (device, n rows of igx_groupby_gather's layout, not
+ * overlapping keys) is the row igx_groupby_gather gives for its slot and found[i] (device u8)
+ * is 1; for any other key -- never inserted, or kept in the table from an earlier interval of
+ * the generation without an event in this one (igx_groupby_reset) -- the row is zero and
+ * found[i] is 0.  Duplicate keys are allowed.  A read-only probe of at most the table's probe
+ * region per key, in every form (cached, direct, partitioned). */
+int igx_groupby_lookup(igx_table *t, const uint8_t *keys, uint32_t key_stride, uint64_t n,
+                       uint8_t *out_rows, uint8_t *found);
 /* Per-interval reset (nextStats' Delete loop, tracer.go:154-171): the next interval's groups,
  * sums and first indices are its own.  Keys themselves are kept across intervals while the
  * table runs its cached form: a recurring key is found instead of inserted again, and only the

@@ -146,6 +146,8 @@ SIGNATURES = [
     ("igx_groupby_wait", _I, [_VP, C.POINTER(C.c_uint64)]),
     ("igx_groupby_info", _I, [_VP, C.POINTER(GroupbyInfo)]),
     ("igx_groupby_gather", _I, [_VP, _VP, _U64, _VP]),
+    ("igx_groupby_select_ge", _I, [_VP, _U32, _U64, _VP, _U64, _VP]),
+    ("igx_groupby_lookup", _I, [_VP, _VP, _U32, _U64, _VP, _VP]),
     ("igx_groupby_sort", _I, [_VP, C.POINTER(TSortKey), _U32, _U32, _VP]),
     ("igx_segment_fsum", _I, [_VP, _VP, _U32, _U32, _VP, _U64, _VP, _VP, _U32, _VP]),
     ("igx_ip_text", _I, [_VP, _VP, _U32, _VP, _U32, _VP, _U64, _VP]),

@@ -2049,6 +2049,95 @@ __global__ void k_gather_rows(const uint8_t *__restrict__ krec, uint32_t krec_le
     }
 }
 
+// ---- threshold selection and key lookup over a finalized table -----------------------------
+// The two device steps of the cross-rank threshold top-K: "which of my groups
+// hold aggregate x >= T" and "what do I hold for these keys in this interval".  Both only read
+// the table.
+
+// the interval's groups (finalize's slot list, its count read here) whose aggregate `agg`,
+// masked to its out_width as k_gather_rows masks it, is >= thr.  *count receives how many
+// qualify (zeroed before the launch); the first cap of them, in the order the waves' atomics
+// land, go to out.  One atomic per wave and sweep step.
+__global__ __launch_bounds__(256) void k_select_ge(const uint32_t *__restrict__ groups, const uint64_t *__restrict__ ng,
+                                                   uint64_t ns, const uint64_t *__restrict__ vrec, uint32_t vw,
+                                                   uint32_t agg, uint64_t mask, uint64_t thr,
+                                                   uint32_t *__restrict__ out, uint64_t cap,
+                                                   unsigned long long *__restrict__ count) {
+    const uint64_t n = min(*ng, ns);
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    const uint32_t lane = threadIdx.x & 63;
+    // whole waves step together (the ballot below needs every lane of the wave in the loop)
+    for (uint64_t r0 = (uint64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); r0 < n; r0 += stride) {
+        const uint64_t r = r0 + lane;
+        uint32_t slot = 0;
+        bool q = false;
+        if (r < n) {
+            slot = groups[r];
+            q = slot < ns && (vrec[(uint64_t)slot * vw + 1 + agg] & mask) >= thr;
+        }
+        const uint64_t b = __ballot(q);
+        if (!b) continue;
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(count, (unsigned long long)__popcll(b));
+        base = __shfl(base, 0);
+        const uint64_t pos = base + (uint64_t)__popcll(b & ((1ull << lane) - 1));
+        if (q && pos < cap) out[pos] = slot;
+    }
+}
+
+// Query i's key (KW words, those past key_words zero, as the update kernels lay a key out) is
+// probed in the table's current generation like k_gb_seeds probes a seed: read-only, the chain
+// ends at the generation's first empty slot or after max_probe slots.  A key record that is
+// found is a group of this interval only if finalize listed its slot (the occupancy bitmap:
+// a key kept from an earlier interval of the generation has its record but no bit).  Found:
+// out row = k_gather_rows' row of the slot, found[i] = 1; else a zero row and 0.
+template <int KW>
+__global__ __launch_bounds__(256) void k_gb_lookup(GbArgs a, const uint8_t *__restrict__ qkeys, uint32_t qstride,
+                                                   uint64_t nq, uint32_t key_words, AggMasks am,
+                                                   uint8_t *__restrict__ out, uint8_t *__restrict__ found) {
+    constexpr uint32_t KOFF = koff_of(KW);
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    const uint32_t gep = (uint32_t)*a.gen;
+    const uint32_t *qk = reinterpret_cast<const uint32_t *>(qkeys + i * qstride);
+    uint32_t k[KW];
+#pragma unroll
+    for (int w = 0; w < KW; ++w) k[w] = (uint32_t)w < key_words ? qk[w] : 0u;
+    const uint64_t h = hash_key<KW>(k);
+    const uint64_t tag = (h & ~EP_MAX) | gep;
+    uint32_t hit = SLOT_OVF;
+    uint64_t s = home_slot(a, h);
+    for (uint32_t probe = 0; probe < a.max_probe; ++probe) {
+        const uint8_t *r = a.krec + s * a.krec_len;
+        const uint64_t t = *reinterpret_cast<const uint64_t *>(r + KOFF);
+        if ((t & EP_MAX) != gep) break;   // an empty slot of the generation: the key is not there
+        if (t == tag && ready_pub(*reinterpret_cast<const uint64_t *>(r + KOFF + 8), gep, a.ep)) {
+            bool eq = true;
+#pragma unroll
+            for (int w = 0; w < KW; ++w) eq = eq && reinterpret_cast<const uint32_t *>(r)[w] == k[w];
+            if (eq) {
+                hit = (uint32_t)s;
+                break;
+            }
+        }
+        s = next_slot(a, s);
+    }
+    const bool ok = hit != SLOT_OVF && ((a.occ[hit >> 5] >> (hit & 31)) & 1u);
+    const uint32_t row_words = key_words + 2 * a.naggs + 2;
+    uint32_t *o = reinterpret_cast<uint32_t *>(out) + i * row_words;
+    const uint32_t *val = reinterpret_cast<const uint32_t *>(a.vrec + (uint64_t)(ok ? hit : 0u) * a.vrec_words);
+    for (uint32_t w = 0; w < row_words; ++w) {
+        uint32_t v = 0;
+        if (ok) {
+            if (w < key_words) v = qk[w];
+            else if (w < key_words + 2 * a.naggs) v = val[2 + (w - key_words)] & am.m[w - key_words];
+            else v = val[w - key_words - 2 * a.naggs];
+        }
+        o[w] = v;
+    }
+    found[i] = ok ? 1 : 0;
+}
+
 // rows kept by `in` (nullable: all) and every predicate of dp -> out (u8; in may be out)
 __global__ __launch_bounds__(256) void k_pred_mask(DevPreds dp, const uint8_t *in, uint64_t n, uint8_t *out) {
     const uint64_t stride = (uint64_t)gridDim.x * 256;
@@ -2089,6 +2178,7 @@ struct igx_table {
     uint64_t ep = 0;             // current epoch (1..EP_MAX)
     bool persist = true;         // keys outlive their interval (IGX_GB_PERSIST=0: every reset starts a generation)
     bool fin_since_update = false;   // a finalize listed the groups after the last update
+    bool fin_current = false;    // ... and no reset since: the slot list and the bitmap are the interval's
     bool gen_planned = false;    // the reset let the interval continue the generation (device decides by key count)
     bool seed_on = true;         // sample-seeded LDS cache for kept keys (IGX_GB_SEED=0: off)
     igx_table *seed_tab = nullptr;   // the row sample's counting table
@@ -2323,6 +2413,7 @@ extern "C" int igx_groupby_reset(igx_table *t) {
     IGX_HIP(ctx, hipGetLastError());
     t->rows_fed = 0;
     t->host_groups = 0;
+    t->fin_current = false;
     return pending_rc;
 }
 
@@ -2915,6 +3006,7 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
         return igx_fail(ctx, IGX_EINVAL, "groupby_update: event indices reach 2^48 (rebase the interval's indices)");
     t->rows_fed += nrows;
     t->fin_since_update = false;
+    t->fin_current = false;
     GbArgs a{};
     uint32_t w = 0;
     for (uint32_t k = 0; k < t->nkeys; ++k) {
@@ -3208,6 +3300,7 @@ static int fin_launch(igx_table *t) {
                        t->tile_cnt, t->occb_dirty ? t->occb : (uint8_t *)nullptr);
     t->occb_dirty = false;
     t->fin_since_update = true;
+    t->fin_current = true;
     // the kernel that finds the group count also writes the read-back into fin_host
     const uint64_t seq = ++t->fin_seq;
     t->fin_snap.rows_fed = t->rows_fed;
@@ -3385,6 +3478,78 @@ extern "C" int igx_groupby_gather(igx_table *t, const uint32_t *idx, uint64_t k,
     }
     hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)k), dim3(64), 0, ctx->stream, t->krec, t->krec_len, t->vrec,
                        t->vrec_len / 8, t->key_words, t->naggs, am, idx, t->nslots, k, out_rows);
+    IGX_HIP(ctx, hipGetLastError());
+    return IGX_OK;
+}
+
+static uint64_t agg_out_mask(const igx_table *t, uint32_t x) {
+    const uint32_t ow = t->aggs[x].out_width;
+    return (ow == 0 || ow >= 8) ? ~0ull : ((1ull << (8 * ow)) - 1);
+}
+
+extern "C" int igx_groupby_select_ge(igx_table *t, uint32_t agg, uint64_t threshold, uint32_t *out_slots,
+                                     uint64_t cap, uint64_t *d_count) {
+    if (!t) return IGX_EINVAL;
+    igx_ctx *ctx = t->ctx;
+    if (!d_count || (cap && !out_slots)) return igx_fail(ctx, IGX_EINVAL, "groupby_select_ge: null argument");
+    if (agg >= t->naggs) return igx_fail(ctx, IGX_EINVAL, "groupby_select_ge: aggregate %u of %u", agg, t->naggs);
+    if (!t->fin_current) return igx_fail(ctx, IGX_EINVAL, "groupby_select_ge: the interval is not finalized");
+    IGX_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
+    // the group count is on the device: blocks for the most groups the table can list
+    const uint64_t most = std::min<uint64_t>(t->cap, t->nslots);
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)std::max(1, ctx->num_cus * 4), (most + 255) / 256);
+    hipLaunchKernelGGL(k_select_ge, dim3(blocks), dim3(256), 0, ctx->stream, t->groups, t->n_groups, t->nslots, t->vrec,
+                       t->vrec_len / 8, agg, agg_out_mask(t, agg), threshold, out_slots, cap,
+                       reinterpret_cast<unsigned long long *>(d_count));
+    IGX_HIP(ctx, hipGetLastError());
+    return IGX_OK;
+}
+
+template <int KW>
+static void launch_lookup(igx_ctx *ctx, const GbArgs &a, const uint8_t *keys, uint32_t key_stride, uint64_t n,
+                          uint32_t key_words, const AggMasks &am, uint8_t *out_rows, uint8_t *found) {
+    hipLaunchKernelGGL(k_gb_lookup<KW>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a, keys,
+                       key_stride, n, key_words, am, out_rows, found);
+}
+
+extern "C" int igx_groupby_lookup(igx_table *t, const uint8_t *keys, uint32_t key_stride, uint64_t n,
+                                  uint8_t *out_rows, uint8_t *found) {
+    if (!t) return IGX_EINVAL;
+    igx_ctx *ctx = t->ctx;
+    if (n == 0) return IGX_OK;
+    if (!keys || !out_rows || !found) return igx_fail(ctx, IGX_EINVAL, "groupby_lookup: null argument");
+    if (n >= (1ull << 32)) return igx_fail(ctx, IGX_EINVAL, "groupby_lookup: more than 2^32 keys");
+    if (key_stride < t->key_words * 4 || (key_stride & 3) || (reinterpret_cast<uintptr_t>(keys) & 3) ||
+        (reinterpret_cast<uintptr_t>(out_rows) & 3))
+        return igx_fail(ctx, IGX_EINVAL, "groupby_lookup: keys must be 4-byte aligned, key_stride a multiple of 4 "
+                                         "and at least %u", t->key_words * 4);
+    if (!t->fin_current) return igx_fail(ctx, IGX_EINVAL, "groupby_lookup: the interval is not finalized");
+    GbArgs a{};   // the table's side of the update kernels' arguments: the probe reads nothing else
+    a.naggs = t->naggs;
+    a.krec = t->krec;
+    a.vrec = t->vrec;
+    a.krec_len = t->krec_len;
+    a.vrec_words = t->vrec_len / 8;
+    a.occ = t->occ;
+    a.ep = t->ep;
+    a.gen = reinterpret_cast<uint64_t *>(t->err) + GEN_WORD;
+    a.sshift = 64 - t->sbits;
+    a.rmask = (1ull << t->rbits) - 1;
+    a.max_probe = 1u << t->rbits;
+    AggMasks am{};
+    for (uint32_t x = 0; x < t->naggs; ++x) {
+        const uint64_t m = agg_out_mask(t, x);
+        am.m[2 * x] = (uint32_t)m;
+        am.m[2 * x + 1] = (uint32_t)(m >> 32);
+    }
+    switch (t->kw_rec) {   // every key-record width a table can have: the static layouts' and kInst
+#define IGX_LOOKUP_KW(KW) \
+    case KW: launch_lookup<KW>(ctx, a, keys, key_stride, n, t->key_words, am, out_rows, found); break;
+    IGX_LOOKUP_KW(1) IGX_LOOKUP_KW(2) IGX_LOOKUP_KW(4) IGX_LOOKUP_KW(5) IGX_LOOKUP_KW(6) IGX_LOOKUP_KW(8)
+    IGX_LOOKUP_KW(10) IGX_LOOKUP_KW(12) IGX_LOOKUP_KW(18) IGX_LOOKUP_KW(24) IGX_LOOKUP_KW(32)
+#undef IGX_LOOKUP_KW
+    default: return igx_fail(ctx, IGX_ENOTSUP, "groupby_lookup: no kernel for %u key words", t->kw_rec);
+    }
     IGX_HIP(ctx, hipGetLastError());
     return IGX_OK;
 }

@@ -18,6 +18,9 @@ Only data movement and bookkeeping live here; every aggregation and merge runs i
   top-K (C2, C5)            per-rank K candidates -> all-gather -> one more top-K with
                             the global first index as the position                     exact
                             (keys are rank-disjoint after the exchange or by ingest)
+  top-K by a DESC sum (C5)  topk_threshold: local top-K, groups above a threshold, then the
+                            union's keys looked up on every rank -- three all-gathers of a few
+                            dozen rows instead of the group exchange                   exact
 
 The reference merges nodes by concatenating per-node arrays (snapshotcombiner.go:79-106);
 an exact global merge is stricter and equal to the single-device result on the union.
@@ -357,3 +360,236 @@ def merge_topk(cand, key_bytes, naggs, sort_keys, k, c=None):
     first = allc[:, o + 8 * naggs:o + 8 * naggs + 8].contiguous().view(torch.uint64).flatten()
     idx = engine.sort_perm(keys, allc.shape[0], pos=first, k=k)
     return engine.take([allc], idx)[0]
+
+
+# ------------------------------------------------------------------------------------
+# exact top-K across ranks by threshold instead of a full group exchange
+# ------------------------------------------------------------------------------------
+# "Top K by a DESC sum of non-negative partials" does not need every partial group at its owner:
+# three small rounds (TPUT-style) give the same K rows, ties at the K-th value included.
+#   round 1  local top-K rows, all-gathered, merged by key: tau = the K-th largest merged value
+#            (a lower bound of the global K-th value: partial sums only grow)
+#   round 2  every rank lists its groups with a local value >= T = ceil(tau / ws)
+#            (igx_groupby_select_ge); their keys' union U holds every group whose global value
+#            is >= tau: a group outside U has every local value < tau / ws, so its sum is < tau
+#   round 3  every rank reports what it holds for U's keys (igx_groupby_lookup); merged by key
+#            (SUM, MIN of first) these are U's exact global rows; their top-K is the answer
+# The rounds are transport-free functions over packed rows; topk_threshold joins them with
+# allgather_rows, topk_threshold_ranks plays N ranks in one process by concatenation.
+U64_MAX = (1 << 64) - 1
+
+
+def _key_bytes(key_widths):
+    return sum((w + 3) // 4 * 4 for w in key_widths)
+
+
+def _agg_host(rows, kb, x):
+    """aggregate x of packed rows as a host u64 array"""
+    import numpy as np
+    a = rows[:, kb + 8 * x:kb + 8 * x + 8].contiguous().cpu().numpy()
+    return a.copy().view(np.uint64).ravel()
+
+
+def group_rows(table):
+    """Every group of a finalized table as packed rows (key | aggregates | first index)."""
+    torch = torch_mod()
+    fin = table.fin
+    G = fin["n_groups"]
+    if G is None:
+        G = table.wait()
+    slots = torch.empty(max(1, G), dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))[:G]
+    if G:
+        table.ctx.check(table.ctx.L.igx_memcpy_d2d(table.ctx.h, ptr(slots), C.c_void_p(fin["groups_ptr"]), G * 4))
+    return table.gather(slots)
+
+
+def tt_applies(table, sort_keys):
+    """None when the threshold protocol can answer this sort spec on this table, else why not:
+    the first sort key must be a DESC aggregate (COUNT or SUM: non-negative partials whose sum
+    is the global value) that does not wrap below 8 bytes."""
+    from . import _abi
+    if not sort_keys:
+        return "no sort key"
+    src, what, desc = sort_keys[0]
+    if src != _abi.TSRC_AGG:
+        return "the first sort key is not an aggregate"
+    if not desc:
+        return "the first sort key is ascending"
+    if table.out_widths[int(what or 0)] != 8:
+        return "the first sort key's aggregate wraps below 8 bytes"
+    return None
+
+
+def tt_candidates(table, sort_keys, k):
+    """Round 1, per rank: the local top-K as packed rows (the table is synchronously finalized)."""
+    if table.fin["n_groups"] is None:
+        table.wait()
+    return table.gather(table.sort(sort_keys, k))
+
+
+def tt_threshold(cand, ws, sort_keys, k, key_widths, out_widths, table=None):
+    """Round 1, every rank alike: all ranks' candidates -> the decision.  {"path": "threshold",
+    "tau", "T"} or {"path": "full", "reason"}: a global sum that could wrap (the largest local
+    value M > (2^64 - 1) // ws), fewer than k candidate groups (then there are fewer than k
+    groups in all), or tau == 0 (T would select every group).  table: a merge table to reuse."""
+    import numpy as np
+    torch = torch_mod()
+    x, kb = int(sort_keys[0][1] or 0), _key_bytes(key_widths)
+    if cand.shape[0] < 1:
+        return {"path": "full", "reason": "fewer than k groups", "tau": None}
+    merged = merge_partials(cand, key_widths, out_widths, max(1, cand.shape[0]), table=table)
+    try:
+        # the candidates' local values and the merged values in one host read
+        both = torch.cat([cand, group_rows(merged)])
+    finally:
+        if table is None:
+            merged.destroy()
+    v = _agg_host(both, kb, x)
+    M, vals = int(v[:cand.shape[0]].max()), np.sort(v[cand.shape[0]:])[::-1]
+    if M > U64_MAX // ws:
+        return {"path": "full", "reason": "a global sum could wrap 2^64", "tau": None}
+    if len(vals) < k:
+        return {"path": "full", "reason": "fewer than k groups", "tau": None}
+    tau = int(vals[k - 1])
+    if tau == 0:
+        return {"path": "full", "reason": "tau == 0", "tau": 0}
+    return {"path": "threshold", "tau": tau, "T": -(-tau // ws)}
+
+
+def tt_select(table, sort_keys, T, cand_cap):
+    """Round 2, per rank: (slots, count) of the groups whose first-sort-key value is >= T;
+    count > cand_cap means the list is cut and every rank must fall back."""
+    return table.select_ge(int(sort_keys[0][1] or 0), T, cand_cap)
+
+
+def tt_count_row(count, device):
+    """A rank's round-2 count as the one 8-byte row it all-gathers first."""
+    torch = torch_mod()
+    return torch.tensor([count], dtype=torch.int64, device=device).view(torch.uint8).reshape(1, 8)
+
+
+def tt_counts(count_rows):
+    """The all-gathered count rows -> [count per rank]."""
+    torch = torch_mod()
+    return [int(v) for v in count_rows.contiguous().cpu().view(torch.int64).ravel().tolist()]
+
+
+def tt_union(sel, key_widths, out_widths, table=None):
+    """Round 2, every rank alike: all ranks' selected rows -> one row per distinct key (the
+    union U; only the keys are used)."""
+    merged = merge_partials(sel, key_widths, out_widths, max(1, sel.shape[0]), table=table)
+    try:
+        return group_rows(merged).clone()
+    finally:
+        if table is None:
+            merged.destroy()
+
+
+def tt_lookup(table, union):
+    """Round 3, per rank: this rank's rows for U's keys (the keys it does not hold dropped)."""
+    rows, found = table.lookup(union)
+    return rows[found.bool()]
+
+
+def tt_final(rows, sort_keys, k, key_widths, out_widths, table=None):
+    """Round 3, every rank alike: all ranks' rows for U (or, on the full path, the owners'
+    candidates) merged by key -- SUM of the partials, MIN of the first indices -- and their
+    top-K under the whole sort spec, as packed rows."""
+    merged = merge_partials(rows, key_widths, out_widths, max(1, rows.shape[0]), table=table)
+    try:
+        return merged.gather(merged.sort(sort_keys, k)).clone()
+    finally:
+        if table is None:
+            merged.destroy()
+
+
+def topk_scratch(key_widths, out_widths, ws, k, cand_cap):
+    """The three small merge tables of the protocol, to reuse across steps (without them every
+    call creates and frees its own): {"r1", "r2", "r3"} for tt_threshold, tt_union, tt_final."""
+    return {"r1": owner_table(key_widths, out_widths, ws * k),
+            "r2": owner_table(key_widths, out_widths, ws * cand_cap),
+            "r3": owner_table(key_widths, out_widths, ws * cand_cap)}
+
+
+def _threshold_rounds(tables, ws, join, full, sort_keys, k, key_widths, out_widths, cand_cap, scratch):
+    """The protocol over the ranks this process plays (tables) and `join`, which turns their
+    per-rank rows into all ranks' rows; full(reason, tau) runs the full exchange instead."""
+    s = scratch or {}
+    why = tt_applies(tables[0], sort_keys)
+    if why:
+        return full(why, None)
+    dec = tt_threshold(join([tt_candidates(t, sort_keys, k) for t in tables]), ws, sort_keys, k, key_widths,
+                       out_widths, table=s.get("r1"))
+    if dec["path"] == "full":
+        return full(dec["reason"], dec["tau"])
+    sel = [tt_select(t, sort_keys, dec["T"], cand_cap) for t in tables]
+    dev = sel[0][0].device
+    counts = tt_counts(join([tt_count_row(n, dev) for _, n in sel]))
+    if max(counts) > cand_cap:   # the same counts on every rank: the same decision
+        return full(f"a rank selected more than cand_cap={cand_cap} groups", dec["tau"])
+    union = tt_union(join([t.gather(sl) for t, (sl, _) in zip(tables, sel)]), key_widths, out_widths,
+                     table=s.get("r2"))
+    rows = tt_final(join([tt_lookup(t, union) for t in tables]), sort_keys, k, key_widths, out_widths,
+                    table=s.get("r3"))
+    return rows, {"path": "threshold", "reason": None, "tau": dec["tau"], "T": dec["T"], "sent": counts,
+                  "union": int(union.shape[0]), "cand_cap": cand_cap}
+
+
+def topk_threshold(table, sort_keys, k, key_widths, out_widths, capacity, cand_cap=None, c=None, scratch=None):
+    """Exact global top-K of a per-rank partial table (synchronously finalized) under sort_keys
+    ([(src, what, desc)] as Table.sort takes them), on every rank the same packed rows (key |
+    aggregates | global first index): what exchange_rows -> merge_partials -> the owner's top-K
+    -> merge_topk gives, from three all-gathers of a few dozen rows (see above) when the first
+    sort key is a DESC COUNT / SUM aggregate of out_width 8; any other sort spec, a possible
+    wrap, fewer than k groups, tau == 0 or a rank selecting more than cand_cap (default
+    max(4096, 64 k)) groups takes the full exchange (capacity: the owner table's).  Returns
+    (rows, info): info["path"] is "threshold", "full" (with "reason") or, without a multi-rank
+    group, "local"; "tau", "sent" (rows per rank in round 2) and "union" (|U|) describe the
+    threshold path.  scratch: topk_scratch() tables to reuse."""
+    c = c or comm()
+    if cand_cap is None:
+        cand_cap = max(4096, 64 * k)
+    if c is None:
+        return tt_candidates(table, sort_keys, k), {"path": "local", "reason": None, "tau": None, "sent": None,
+                                                    "union": None}
+    ws = world()[1]
+    kb = _key_bytes(key_widths)
+
+    def full(reason, tau):
+        part, counts = partition_by_owner(group_rows(table), kb, ws)
+        mine = exchange_partitioned(part, counts, c)
+        own = merge_partials(mine, key_widths, out_widths, capacity)
+        try:
+            cand = own.gather(own.sort(sort_keys, k))
+            # the owners' candidates are key-disjoint: merging them by key changes no row, and
+            # its top-K is merge_topk's under sort specs with key columns too
+            rows = tt_final(allgather_rows(cand, c), sort_keys, k, key_widths, out_widths)
+        finally:
+            own.destroy()
+        return rows, {"path": "full", "reason": reason, "tau": tau, "sent": None, "union": None}
+
+    return _threshold_rounds([table], ws, lambda parts: allgather_rows(parts[0], c), full, sort_keys, k,
+                             key_widths, out_widths, cand_cap, scratch)
+
+
+def topk_threshold_ranks(tables, sort_keys, k, key_widths, out_widths, capacity, cand_cap=None, scratch=None):
+    """topk_threshold with one process playing every rank: tables are the ranks' partial
+    tables (synchronously finalized), and the all-gathers are concatenations in rank order (the
+    full exchange: every rank's groups merged in one table of `capacity`).  Same (rows, info)."""
+    torch = torch_mod()
+    ws = len(tables)
+    if cand_cap is None:
+        cand_cap = max(4096, 64 * k)
+    if ws == 1:
+        return tt_candidates(tables[0], sort_keys, k), {"path": "local", "reason": None, "tau": None,
+                                                        "sent": None, "union": None}
+
+    def full(reason, tau):
+        own = merge_partials(torch.cat([group_rows(t) for t in tables]), key_widths, out_widths, capacity)
+        try:
+            rows = own.gather(own.sort(sort_keys, k)).clone()
+        finally:
+            own.destroy()
+        return rows, {"path": "full", "reason": reason, "tau": tau, "sent": None, "union": None}
+
+    return _threshold_rounds(tables, ws, torch.cat, full, sort_keys, k, key_widths, out_widths, cand_cap, scratch)

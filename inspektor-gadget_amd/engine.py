@@ -326,6 +326,46 @@ class Table:
             self.ctx.check(self.ctx.L.igx_groupby_gather(self.h, ptr(slots), k, ptr(out)))
         return out[:k]
 
+    def select_ge(self, agg, threshold, cap, sync=True):
+        """igx_groupby_select_ge: the finalized interval's group slots whose aggregate `agg`
+        (wrapped to its out_width, as gather wraps it) is >= threshold, in no particular order.
+        Returns (slots, count): count is how many qualify; at most cap slots are listed, so
+        count > cap means the list is incomplete.  sync=True reads the count (one host read) and
+        returns slots[:min(count, cap)] and an int; sync=False returns the cap-entry tensor and
+        the count as a device u64 tensor."""
+        torch = torch_mod()
+        ctx = self.ctx
+        ctx.bind_stream()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
+        cnt = torch.empty(1, dtype=torch.uint64, device=dev)
+        ctx.check(ctx.L.igx_groupby_select_ge(self.h, agg, threshold, ptr(out), cap, ptr(cnt)))
+        if not sync:
+            return out[:cap], cnt
+        n = int(cnt.item())
+        return out[:min(n, cap)], n
+
+    def lookup(self, key_rows):
+        """igx_groupby_lookup: key_rows is a device uint8 tensor (n, >= key_bytes) whose rows
+        start with a packed key (rows from gather() can be passed as they are).  Returns (rows,
+        found): rows (n, key_bytes + 8*naggs + 8) as gather() gives them for the keys that are
+        groups of the finalized interval, zero rows for the others; found (n,) uint8."""
+        torch = torch_mod()
+        ctx = self.ctx
+        ctx.bind_stream()
+        kb = sum((w + 3) // 4 * 4 for w in self.key_widths)
+        if key_rows.dim() != 2 or key_rows.dtype != torch.uint8 or key_rows.shape[1] < kb:
+            raise ValueError(f"lookup: key_rows must be uint8 (n, >= {kb})")
+        if key_rows.shape[0] and (key_rows.stride(1) != 1 or key_rows.stride(0) % 4 or key_rows.data_ptr() % 4):
+            key_rows = key_rows[:, :kb].contiguous()   # the C ABI wants 4-byte aligned keys and stride
+        n = key_rows.shape[0]
+        row = kb + 8 * self.naggs + 8
+        out = torch.empty((max(1, n), row), dtype=torch.uint8, device=key_rows.device)
+        found = torch.empty(max(1, n), dtype=torch.uint8, device=key_rows.device)
+        if n:
+            ctx.check(ctx.L.igx_groupby_lookup(self.h, ptr(key_rows), key_rows.stride(0), n, ptr(out), ptr(found)))
+        return out[:n], found[:n]
+
     def partition(self, nparts, out_widths=None):
         """igx_partition_groups: the finalized table's groups as packed rows (key | aggregates
         wrapped to out_widths | first index), grouped by owner part (FNV-1a over the key words
