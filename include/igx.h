@@ -148,7 +148,11 @@ int igx_version(void);
 /* ---- filter (host parser + device scan) -------------------------------------------- */
 /* GetFilterFromString: parses "col[:[!][~|>=|>|<=|<]value]".  Host only, no GPU needed.
  * Regex rules are returned with cmp=IGX_CMP_REGEX and value = the pattern; igx_filter
- * compiles and runs them (below).  errbuf receives the Go error text. */
+ * compiles and runs them (below).  errbuf receives the Go error text.  Numbers parse as
+ * strconv does: ParseInt / ParseUint base 10 (a sign on int columns only), ParseFloat with hex
+ * floats only when they carry a 'p' exponent ("0x1" is rejected) and a sign on inf / infinity
+ * but not on nan ("+nan" is rejected).  A string column may be wider than IGX_MAX_REF: the
+ * reference then reads as zero bytes past IGX_MAX_REF. */
 int igx_filter_parse(const igx_schema_col *cols, uint32_t ncols, const char *filter,
                      igx_pred *out, char *errbuf, size_t errlen);
 
@@ -307,7 +311,22 @@ int igx_groupby_create(igx_ctx *ctx, const uint32_t *key_widths, uint32_t nkeys,
  * (in the table's key order); preds are AND-ed filters applied first (the BPF probe
  * checks): any number, of any kind igx_filter takes plus IGX_CMP_IN sets (up to two scalar
  * comparisons / sets are fused into the aggregation kernel, the others -- regex, string
- * rules, more comparisons -- first become a device row mask).  base_idx is the global index of row 0 (first-occurrence order); indices must
+ * rules, more comparisons -- first become a device row mask).  An IGX_CMP_IN set is only ever
+ * evaluated in the aggregation kernel: more than two of them in one update return
+ * IGX_ENOTSUP, and so does a guarded set whose guard column is not the cond_col of one of the
+ * table's aggregates (a guard on any other column is evaluated by the row mask, which has no
+ * set test); a set on a float or string column, or with ref_len not a multiple of the column
+ * width, returns IGX_EINVAL.
+ * Alignment (IGX_EINVAL otherwise): a key column of 1 or 2 bytes is aligned to its width, one
+ * of 4, 8 or 12 bytes to 4, a wider multiple of 4 to 16; other widths take any address.  Every other scalar column the update reads -- aggregate value and
+ * condition columns, predicate columns of a non-string kind, guard columns -- and `valid` are
+ * read as the aligned 4-byte words that hold each row, counted from the column's base, so
+ * the base must be 4-byte aligned (8-byte aligned for an 8-byte column): a 1- or 2-byte
+ * column that starts at an odd row of a larger buffer is rejected with IGX_EINVAL (its words
+ * would be misaligned and would run up to three bytes past its last row); copy such a slice
+ * first.  The bytes up to the next 4-byte boundary after a column's last row are read and must
+ * be readable, which holds for any HIP allocation.  String predicate columns take any address.
+ * base_idx is the global index of row 0 (first-occurrence order); indices must
  * stay below 2^48 - 1 (IGX_EINVAL otherwise; an index column value at or above it fails the
  * interval at finalize): long-running streams rebase their indices per interval.  Async. */
 int igx_groupby_update(igx_table *t, const igx_col *cols, uint32_t ncols,

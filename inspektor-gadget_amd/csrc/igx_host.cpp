@@ -241,7 +241,10 @@ bool parse_float64(const std::string &s, double *out) {
     std::string l = lower(s);
     std::string body = (l[0] == '+' || l[0] == '-') ? l.substr(1) : l;
     if (body == "inf" || body == "infinity") { *out = l[0] == '-' ? -INFINITY : INFINITY; return true; }
-    if (body == "nan") { *out = NAN; return true; }
+    // strconv's special() takes a sign only before "inf": "+nan" / "-nan" are syntax errors
+    if (body == "nan") { if (body.size() != l.size()) return false; *out = NAN; return true; }
+    // a hexadecimal mantissa needs a 'p' exponent (strtod would take "0x1" as 1)
+    if (body.rfind("0x", 0) == 0 && body.find('p') == std::string::npos) return false;
     for (char c : l)
         if (!(std::isdigit((unsigned char)c) || c == '.' || c == 'e' || c == '+' || c == '-' || c == 'x' ||
               c == 'p' || (c >= 'a' && c <= 'f')))

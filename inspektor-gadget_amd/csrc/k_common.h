@@ -46,17 +46,21 @@ __device__ __forceinline__ int pred_cmp(const DevPred &d, uint64_t row) {
     if (d.kind == IGX_KIND_BYTES) {
         const uint8_t *f = d.ptr + row * d.width;
         // d.ref_len > width cannot be equal; compare the common prefix then lengths
+        // a column wider than the reference buffer: the reference bytes at or past IGX_MAX_REF
+        // are zero (a value with a byte there is greater), never read from d.ref
         uint32_t n = d.width;
         if ((n & 3) == 0 && (((uintptr_t)f) & 3) == 0) {
             for (uint32_t w = 0; w < n / 4; ++w) {
                 uint32_t a = __builtin_bswap32(*reinterpret_cast<const uint32_t *>(f + 4 * w));
-                uint32_t b = ((uint32_t)d.ref[4 * w] << 24) | ((uint32_t)d.ref[4 * w + 1] << 16) |
-                             ((uint32_t)d.ref[4 * w + 2] << 8) | d.ref[4 * w + 3];
+                uint32_t b = 4 * w < IGX_MAX_REF
+                                 ? ((uint32_t)d.ref[4 * w] << 24) | ((uint32_t)d.ref[4 * w + 1] << 16) |
+                                       ((uint32_t)d.ref[4 * w + 2] << 8) | d.ref[4 * w + 3]
+                                 : 0u;
                 if (a != b) return a < b ? -1 : 1;
             }
         } else {
             for (uint32_t i = 0; i < n; ++i) {
-                uint8_t a = f[i], b = d.ref[i];
+                uint8_t a = f[i], b = i < IGX_MAX_REF ? d.ref[i] : (uint8_t)0;
                 if (a != b) return a < b ? -1 : 1;
             }
         }

@@ -3039,6 +3039,15 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
         a.koff[w] = 0;
         a.kmask[w] = 0;
     }
+    // Scalar columns other than keys (aggregate values and conditions, predicates, guards, the
+    // nil mask) are read as the aligned dwords that hold each row, formed from the column's
+    // base: a base off a 4-byte boundary would make them misaligned loads that run up to three
+    // bytes past the column's last 4-byte block.
+    auto misaligned = [](const igx_col &c) {
+        return (reinterpret_cast<uintptr_t>(c.ptr) & (c.width == 8 ? 7u : 3u)) != 0;
+    };
+    if (valid && (reinterpret_cast<uintptr_t>(valid) & 3u))
+        return igx_fail(ctx, IGX_EINVAL, "groupby_update: valid mask misaligned");
     a.naggs = t->naggs;
     for (uint32_t x = t->naggs; x < AMAX; ++x) {   // unused slots are still loaded (issue_row)
         a.vptr[x] = a.cptr[x] = dummy;
@@ -3058,6 +3067,8 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
                 return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: agg width %u", a.vwidth[x]);
             if (cols[g.col].kind == IGX_KIND_FLOAT)
                 return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: float sums are not supported");
+            if (misaligned(cols[g.col]))
+                return igx_fail(ctx, IGX_EINVAL, "groupby_update: value column of aggregate %u misaligned", x);
             if (g.divisor > 1) {
                 if (a.vsign[x])
                     return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: divisor on a signed column");
@@ -3071,6 +3082,8 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
             const uint32_t cw = cols[g.cond_col].width;
             if (cw != 1 && cw != 2 && cw != 4 && cw != 8)
                 return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: condition width %u", cw);
+            if (misaligned(cols[g.cond_col]))
+                return igx_fail(ctx, IGX_EINVAL, "groupby_update: condition column of aggregate %u misaligned", x);
             a.cptr[x] = static_cast<const uint8_t *>(cols[g.cond_col].ptr);
             a.cwidth[x] = cw;
             a.cval[x] = cw == 8 ? g.cond_val : (g.cond_val & ((1ull << (8 * cw)) - 1));
@@ -3121,6 +3134,17 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
         if (preds[p].guard_len) {
             const int rc = igx_check_guard(ctx, cols, ncols, preds[p]);
             if (rc) return rc;
+            if (misaligned(cols[preds[p].guard_col]))
+                return igx_fail(ctx, IGX_EINVAL, "groupby_update: guard column of predicate %u misaligned", p);
+        }
+        if (cols[preds[p].col].kind != IGX_KIND_BYTES && misaligned(cols[preds[p].col]))
+            return igx_fail(ctx, IGX_EINVAL, "groupby_update: predicate column %u misaligned", p);
+        if (preds[p].cmp == IGX_CMP_IN && !fusable(preds[p])) {   // the mask scan has no set test
+            if (preds[p].guard_len && guard_agg(preds[p]) == AMAX)
+                return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: IN predicate %u is guarded by a column that is no "
+                                                  "aggregate's condition column (not supported)", p);
+            return igx_fail(ctx, IGX_EINVAL, "groupby_update: IN predicate %u needs an integer column of 1, 2, 4 "
+                                             "or 8 bytes", p);
         }
         (fusable(preds[p]) ? fused : masked).push_back(preds[p]);
     }

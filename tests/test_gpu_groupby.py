@@ -413,7 +413,7 @@ def test_merge_partials_on_device(oracle, E, H, igx, torch):
     widths = [8, 4, 4, 4]
     aggs = [A.Agg(A.AGG_COUNT, 0, 4, 8, 1), A.Agg(A.AGG_SUM, 5, 4, 4, 1)]
     rows = []
-    cuts = [0, 70_001, 190_000, n]
+    cuts = [0, 70_004, 190_000, n]   # uneven shards; multiples of 4 rows: `op` (u8) must start 4-byte aligned
     for a, b in zip(cuts[:-1], cuts[1:]):
         t = E.Table(widths, aggs, 2 * G)
         t.update([ev[k][a:b] for k in names], [0, 1, 2, 3], b - a, a)
