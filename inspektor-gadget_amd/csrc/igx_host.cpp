@@ -462,15 +462,9 @@ int igx_check_guard(igx_ctx *ctx, const igx_col *cols, uint32_t ncols, const igx
     const igx_col &g = cols[p.guard_col];
     if (g.kind != IGX_KIND_INT && g.kind != IGX_KIND_UINT)
         return igx_fail(ctx, IGX_EINVAL, "predicate guard on a non-integer column");
-    if (p.guard_len != g.width || (g.width != 1 && g.width != 2 && g.width != 4 && g.width != 8))
+    if (p.guard_len != g.width || !igx_scalar_width(g.width))
         return igx_fail(ctx, IGX_EINVAL, "predicate guard of %u bytes on a %u-byte column", p.guard_len, g.width);
     return IGX_OK;
-}
-
-uint64_t igx_guard_ref(const igx_pred &p) {
-    uint64_t r = 0;
-    for (uint32_t b = 0; b < p.guard_len && b < 8; ++b) r |= (uint64_t)p.guard_ref[b] << (8 * b);
-    return r;
 }
 
 int igx_build_preds(igx_ctx *ctx, const igx_col *cols, uint32_t ncols, const igx_pred *preds,
@@ -498,17 +492,18 @@ int igx_build_preds(igx_ctx *ctx, const igx_col *cols, uint32_t ncols, const igx
         d.ref_len = p.ref_len;
         if (c.kind == IGX_KIND_BOOL || c.kind == IGX_KIND_OTHER)
             return igx_fail(ctx, IGX_EINVAL, "predicate on unsupported column kind");
-        if (c.kind != IGX_KIND_BYTES && c.width != 1 && c.width != 2 && c.width != 4 && c.width != 8)
+        if (c.kind != IGX_KIND_BYTES && !igx_scalar_width(c.width))
             return igx_fail(ctx, IGX_EINVAL, "predicate on a %u-byte scalar", c.width);
         if (c.kind == IGX_KIND_FLOAT && c.width != 4 && c.width != 8)
             return igx_fail(ctx, IGX_EINVAL, "float column width %u", c.width);
         std::memcpy(d.ref, p.ref, IGX_MAX_REF);
+        if (c.kind != IGX_KIND_BYTES) d.ref64 = igx_pack_ref(p.ref, c.width);
         if (p.guard_len) {
             int rc = igx_check_guard(ctx, cols, ncols, p);
             if (rc) return rc;
             d.gptr = static_cast<const uint8_t *>(cols[p.guard_col].ptr);
             d.gwidth = p.guard_len;
-            d.gref = igx_guard_ref(p);
+            d.gref = igx_pack_ref(p.guard_ref, p.guard_len);
         }
     }
     out->n = npreds;
@@ -616,7 +611,7 @@ static int sort_common(igx_ctx *ctx, const igx_sortkey *keys, const uint32_t *st
         if (k.kind == IGX_KIND_BYTES) {
             p.words = (k.width + 3) / 4;
         } else {
-            if (k.width != 1 && k.width != 2 && k.width != 4 && k.width != 8)
+            if (!igx_scalar_width(k.width))
                 return igx_fail(ctx, IGX_EINVAL, "sort: %u-byte scalar key", k.width);
             if (k.kind == IGX_KIND_FLOAT && k.width < 4) return igx_fail(ctx, IGX_EINVAL, "sort: bad float width");
             p.words = k.width == 8 ? 2 : 1;

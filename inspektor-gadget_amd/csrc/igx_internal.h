@@ -65,7 +65,8 @@ struct DevPred {
     const uint8_t *gptr;  // guard column (igx_pred.guard_*): the test applies where it equals gref
     uint64_t gref;
     uint32_t gwidth, gpad;   // gwidth 0: unguarded
-    uint8_t ref[IGX_MAX_REF];
+    uint64_t ref64;          // int, uint and float columns: the reference's `width` bytes, zero-extended
+    uint8_t ref[IGX_MAX_REF];   // string and regex rules
 };
 struct DevPreds {
     uint32_t n, pad;
@@ -73,9 +74,23 @@ struct DevPreds {
 };
 int igx_build_preds(igx_ctx *ctx, const igx_col *cols, uint32_t ncols, const igx_pred *preds,
                     uint32_t npreds, DevPreds *out);
-// a predicate's guard (igx_pred.guard_*): validated against the columns; its value as u64
+// a predicate's guard (igx_pred.guard_*), validated against the columns
 int igx_check_guard(igx_ctx *ctx, const igx_col *cols, uint32_t ncols, const igx_pred &p);
-uint64_t igx_guard_ref(const igx_pred &p);
+
+// the first n (at most 8) little-endian bytes of a predicate's reference or guard value as u64
+static inline uint64_t igx_pack_ref(const uint8_t *bytes, uint32_t n) {
+    uint64_t r = 0;
+    for (uint32_t b = 0; b < n && b < 8; ++b) r |= (uint64_t)bytes[b] << (8 * b);
+    return r;
+}
+// the widths a scalar column can have
+static inline bool igx_scalar_width(uint32_t w) { return w == 1 || w == 2 || w == 4 || w == 8; }
+// an ordering or equality comparison on an integer or float column of such a width: what a
+// kernel can evaluate on a loaded value (k_pred.h)
+static inline bool igx_scalar_cmp(uint32_t kind, uint32_t width, uint32_t cmp) {
+    return (kind == IGX_KIND_INT || kind == IGX_KIND_UINT || (kind == IGX_KIND_FLOAT && width >= 4)) &&
+           igx_scalar_width(width) && (cmp == IGX_CMP_EQ || (cmp >= IGX_CMP_LT && cmp <= IGX_CMP_GE));
+}
 
 // ---------------------------------------------------------------------------------
 // launchers (defined in the k_*.hip files)

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "igx_internal.h"
+#include "k_pred.h"
 
 #define IGX_WAVE 64
 
@@ -10,35 +11,14 @@ __device__ __forceinline__ uint64_t lanemask_lt() {
     return lane == 0 ? 0ull : (~0ull >> (64 - lane));
 }
 
-// Load a little-endian scalar of `width` bytes (1,2,4,8) as u64, optionally sign-extended.
-__device__ __forceinline__ uint64_t ld_scalar(const uint8_t *p, uint32_t width, uint64_t row,
-                                              bool sign) {
+// Load a little-endian scalar of `width` bytes (1,2,4,8) as u64, zero-extended.
+__device__ __forceinline__ uint64_t ld_scalar(const uint8_t *p, uint32_t width, uint64_t row) {
     switch (width) {
-    case 1: {
-        uint8_t v = p[row];
-        return sign ? (uint64_t)(int64_t)(int8_t)v : v;
+    case 1: return p[row];
+    case 2: return reinterpret_cast<const uint16_t *>(p)[row];
+    case 4: return reinterpret_cast<const uint32_t *>(p)[row];
+    default: return reinterpret_cast<const uint64_t *>(p)[row];
     }
-    case 2: {
-        uint16_t v = reinterpret_cast<const uint16_t *>(p)[row];
-        return sign ? (uint64_t)(int64_t)(int16_t)v : v;
-    }
-    case 4: {
-        uint32_t v = reinterpret_cast<const uint32_t *>(p)[row];
-        return sign ? (uint64_t)(int64_t)(int32_t)v : v;
-    }
-    default:
-        return reinterpret_cast<const uint64_t *>(p)[row];
-    }
-}
-
-__device__ __forceinline__ uint64_t ref_scalar(const DevPred &d, bool sign) {
-    uint64_t v = 0;
-    for (uint32_t b = 0; b < d.width && b < 8; ++b) v |= (uint64_t)d.ref[b] << (8 * b);
-    if (sign && d.width < 8) {
-        uint64_t m = 1ull << (8 * d.width - 1);
-        v = (v ^ m) - m;
-    }
-    return v;
 }
 
 // three-way compare of row vs reference; returns 2 for unordered (NaN).
@@ -67,28 +47,7 @@ __device__ __forceinline__ int pred_cmp(const DevPred &d, uint64_t row) {
         // equal over the column width: a longer reference is greater
         return d.ref_len > n ? -1 : 0;
     }
-    if (d.kind == IGX_KIND_FLOAT) {
-        double a, b;
-        if (d.width == 4) {
-            float x = reinterpret_cast<const float *>(d.ptr)[row];
-            float y;
-            __builtin_memcpy(&y, d.ref, 4);
-            a = x;
-            b = y;
-        } else {
-            a = reinterpret_cast<const double *>(d.ptr)[row];
-            __builtin_memcpy(&b, d.ref, 8);
-        }
-        if (a != a || b != b) return 2;
-        return a < b ? -1 : (a > b ? 1 : 0);
-    }
-    bool sign = d.kind == IGX_KIND_INT;
-    uint64_t a = ld_scalar(d.ptr, d.width, row, sign), b = ref_scalar(d, sign);
-    if (sign) {
-        int64_t x = (int64_t)a, y = (int64_t)b;
-        return x < y ? -1 : (x > y ? 1 : 0);
-    }
-    return a < b ? -1 : (a > b ? 1 : 0);
+    return pred_cmp3(ld_scalar(d.ptr, d.width, row), d.ref64, d.width, d.kind);
 }
 
 // regexp.MatchString over a fixed-width string column (filter.go:212-216): the value is
@@ -165,18 +124,7 @@ __device__ __forceinline__ bool pred_match(const DevPred &d, uint64_t row) {
         if (g != d.gref) return true;
     }
     if (d.cmp == IGX_CMP_REGEX) return regex_match(d.dfa, d.ptr + row * d.width, d.width) != (d.negate != 0);
-    int c = pred_cmp(d, row);
-    bool r;
-    if (c == 2) r = false;
-    else switch (d.cmp) {
-        case IGX_CMP_EQ: r = c == 0; break;
-        case IGX_CMP_LT: r = c < 0; break;
-        case IGX_CMP_LE: r = c <= 0; break;
-        case IGX_CMP_GT: r = c > 0; break;
-        case IGX_CMP_GE: r = c >= 0; break;
-        default: r = false;
-        }
-    return r != (d.negate != 0);
+    return pred_op(pred_cmp(d, row), d.cmp, d.negate);
 }
 
 __device__ __forceinline__ bool preds_match_all(const DevPreds &dp, uint64_t row) {

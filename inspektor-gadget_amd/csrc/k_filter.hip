@@ -66,27 +66,6 @@ __global__ __launch_bounds__(TB) void k_filter_mark(DevPreds dp, const uint8_t *
 // before any is compared, so a tile's loads retire under one wait.  (The generic kernel's
 // short-circuit AND puts each predicate's load behind the previous one's branch: C1's two
 // predicates over 1M rows, 17 us.)
-__device__ __forceinline__ bool pred_eval_int(const DevPred &d, uint64_t a) {
-    const bool sign = d.kind == IGX_KIND_INT;
-    if (sign && d.width < 8) {
-        const uint64_t m = 1ull << (8 * d.width - 1);
-        a = (a ^ m) - m;
-    }
-    const uint64_t b = ref_scalar(d, sign);
-    const int c = sign ? ((int64_t)a < (int64_t)b ? -1 : ((int64_t)a > (int64_t)b ? 1 : 0))
-                       : (a < b ? -1 : (a > b ? 1 : 0));
-    bool r;
-    switch (d.cmp) {
-    case IGX_CMP_EQ: r = c == 0; break;
-    case IGX_CMP_LT: r = c < 0; break;
-    case IGX_CMP_LE: r = c <= 0; break;
-    case IGX_CMP_GT: r = c > 0; break;
-    case IGX_CMP_GE: r = c >= 0; break;
-    default: r = false;
-    }
-    return r != (d.negate != 0);
-}
-
 __global__ __launch_bounds__(TB) void k_filter_mark_int(DevPreds dp, const uint8_t *__restrict__ valid,
                                                         uint64_t n, uint64_t *__restrict__ mask,
                                                         uint32_t *__restrict__ tile_cnt, uint32_t any,
@@ -103,7 +82,7 @@ __global__ __launch_bounds__(TB) void k_filter_mark_int(DevPreds dp, const uint8
         nb[j] = valid ? valid[r] : 1u;
 #pragma unroll
         for (int p = 0; p < IGX_KMAX_PREDS; ++p)
-            v[j][p] = (uint32_t)p < dp.n ? ld_scalar(dp.p[p].ptr, dp.p[p].width, r, false) : 0ull;
+            v[j][p] = (uint32_t)p < dp.n ? ld_scalar(dp.p[p].ptr, dp.p[p].width, r) : 0ull;
     }
     uint32_t cnt = 0;
 #pragma unroll
@@ -117,7 +96,10 @@ __global__ __launch_bounds__(TB) void k_filter_mark_int(DevPreds dp, const uint8
 #pragma unroll
             for (int p = 0; p < IGX_KMAX_PREDS; ++p) {
                 if ((uint32_t)p < dp.n) {
-                    const bool r = pred_eval_int(dp.p[p], v[j][p]);
+                    const DevPred &d = dp.p[p];
+                    // integer kinds only: saying so drops the float compare from the kernel
+                    const uint32_t kind = d.kind == IGX_KIND_INT ? IGX_KIND_INT : IGX_KIND_UINT;
+                    const bool r = pred_op(pred_cmp3(v[j][p], d.ref64, d.width, kind), d.cmp, d.negate);
                     m = any ? (m || r) : (m && r);
                 }
             }
@@ -266,10 +248,7 @@ int launch_filter_chunks(igx_ctx *ctx, const DevPreds *dps, uint32_t nchunks, ui
         bool ints = true;   // integer predicates only: the kernel that loads before it compares
         for (uint32_t p = 0; p < dps[c].n; ++p) {
             const DevPred &d = dps[c].p[p];
-            ints = ints && (d.kind == IGX_KIND_INT || d.kind == IGX_KIND_UINT) && d.gwidth == 0 &&
-                   (d.width == 1 || d.width == 2 || d.width == 4 || d.width == 8) &&
-                   (d.cmp == IGX_CMP_EQ || d.cmp == IGX_CMP_LT || d.cmp == IGX_CMP_LE || d.cmp == IGX_CMP_GT ||
-                    d.cmp == IGX_CMP_GE);
+            ints = ints && igx_scalar_cmp(d.kind, d.width, d.cmp) && d.kind != IGX_KIND_FLOAT && d.gwidth == 0;
         }
         if (ints)
             hipLaunchKernelGGL(k_filter_mark_int, dim3(ntiles), dim3(TB), 0, ctx->stream, dps[c], valid, nrows,

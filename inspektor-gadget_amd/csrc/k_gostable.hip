@@ -40,7 +40,7 @@ __device__ __forceinline__ bool go_value_lt(const GoKey &k, uint32_t ra, uint32_
         if (k.width == 4) return *reinterpret_cast<const float *>(pa) < *reinterpret_cast<const float *>(pb);
         return *reinterpret_cast<const double *>(pa) < *reinterpret_cast<const double *>(pb);
     }
-    const uint64_t x = ld_scalar(pa, k.width, 0, false), y = ld_scalar(pb, k.width, 0, false);
+    const uint64_t x = ld_scalar(pa, k.width, 0), y = ld_scalar(pb, k.width, 0);
     if (k.kind == IGX_KIND_INT) {
         const uint32_t sh = 64u - 8u * k.width;
         return (int64_t)(x << sh) < (int64_t)(y << sh);

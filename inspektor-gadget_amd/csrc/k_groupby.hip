@@ -239,11 +239,6 @@ __device__ __forceinline__ uint32_t ldw(const uint8_t *base, uint64_t off) {
     return (uint64_t)lo | ((uint64_t)(width == 8 ? hi : 0u) << 32);
 }
 
-__device__ __forceinline__ uint64_t sext(uint64_t v, uint32_t width) {
-    const uint32_t sh = 64u - 8u * width;
-    return sh ? (uint64_t)(((int64_t)(v << sh)) >> sh) : v;
-}
-
 // Key layouts.  StaticLayout<W...> fixes the key column widths at compile time (the
 // reference's BPF key structs: ip_key_t, file_id, the advisor tuple, single columns), so
 // every key load is one typed load (dwordx4 for a 16-byte column) with no descriptors in
@@ -318,39 +313,6 @@ struct GenericLayout {
         }
     }
 };
-
-// FilterSpec on a scalar column, evaluated on an already loaded value
-// (getComparisonFuncForComparisonType, filter.go:236-263: (field OP ref) != negate).
-__device__ __forceinline__ bool pred_scalar(uint64_t v, uint64_t ref, uint32_t width, uint32_t kind,
-                                            uint32_t cmp, uint32_t neg, uint32_t cnt) {
-    if (cmp == IGX_CMP_IN) {   // set membership: cnt values of `width` bytes packed in ref
-        const uint64_t m = width >= 8 ? ~0ull : ((1ull << (8 * width)) - 1);
-        bool in = false;
-        for (uint32_t i = 0; i < cnt; ++i) in = in || v == ((ref >> (8 * width * i)) & m);
-        return in != (neg != 0);
-    }
-    int c;
-    if (kind == IGX_KIND_FLOAT) {
-        double x, y;
-        if (width == 4) {
-            x = __uint_as_float((uint32_t)v);
-            y = __uint_as_float((uint32_t)ref);
-        } else {
-            x = __longlong_as_double((long long)v);
-            y = __longlong_as_double((long long)ref);
-        }
-        c = (x != x || y != y) ? 2 : (x < y ? -1 : (x > y ? 1 : 0));
-    } else if (kind == IGX_KIND_INT) {
-        const int64_t x = (int64_t)sext(v, width), y = (int64_t)sext(ref, width);
-        c = x < y ? -1 : (x > y ? 1 : 0);
-    } else {
-        c = v < ref ? -1 : (v > ref ? 1 : 0);
-    }
-    bool r = c != 2 && ((cmp == IGX_CMP_EQ && c == 0) || (cmp == IGX_CMP_LT && c < 0) ||
-                        (cmp == IGX_CMP_LE && c <= 0) || (cmp == IGX_CMP_GT && c > 0) ||
-                        (cmp == IGX_CMP_GE && c >= 0));
-    return r != (neg != 0);
-}
 
 // A key's home slot is the hash's top bits and linear probing wraps inside the slot's
 // region (table.rbits): a bucket of the partitioned form (also the hash's top bits) then owns
@@ -2274,7 +2236,7 @@ extern "C" int igx_groupby_create(igx_ctx *ctx, const uint32_t *key_widths, uint
     if (naggs > AMAX) return igx_fail(ctx, IGX_ENOTSUP, "groupby_create: more than %d aggregates", AMAX);
     for (uint32_t x = 0; x < naggs; ++x) {
         const uint32_t ow = aggs[x].out_width;
-        if (ow != 0 && ow != 1 && ow != 2 && ow != 4 && ow != 8)
+        if (ow != 0 && !igx_scalar_width(ow))
             return igx_fail(ctx, IGX_EINVAL, "groupby_create: aggregate %u out_width %u", x, ow);
         if (aggs[x].kind != IGX_AGG_COUNT && aggs[x].kind != IGX_AGG_SUM)
             return igx_fail(ctx, IGX_EINVAL, "groupby_create: aggregate %u kind %u", x, aggs[x].kind);
@@ -2829,6 +2791,25 @@ constexpr uint64_t SEED_MIN_ROWS = 8u << 20;    // smaller updates: no seeds (IG
 constexpr uint64_t SEED_SAMPLE = 1u << 20;      // sampled rows: max(1M, rows / SEED_DIV)
 constexpr uint64_t SEED_DIV = 128;
 
+// a table's records, occupancy maps, epoch and probe geometry as the kernels read them
+static void bind_records(const igx_table *t, GbArgs &a) {
+    a.krec = t->krec;
+    a.vrec = t->vrec;
+    a.krec_len = t->krec_len;
+    a.krec_total = (uint32_t)(t->nslots * t->krec_len);
+    a.vrec_words = t->vrec_len / 8;
+    a.vrec_total = t->nslots * t->vrec_len < (1ull << 32) ? (uint32_t)(t->nslots * t->vrec_len) : 0u;
+    a.err = t->err;
+    a.occ = t->occ;
+    a.occb = t->occb;
+    a.ep = t->ep;
+    a.gen = reinterpret_cast<uint64_t *>(t->err) + GEN_WORD;
+    a.sshift = 64 - t->sbits;
+    a.rmask = (1ull << t->rbits) - 1;
+    a.max_probe = 1u << t->rbits;
+    a.dbg_cnt = t->dbg_cnt;
+}
+
 template <class L>
 static int seeds_compute_static(igx_table *t, igx_ctx *ctx, const GbArgs &a) {
     const uint32_t E = gb_entries_for<L>(t->naggs);
@@ -2876,20 +2857,7 @@ static int seeds_compute_static(igx_table *t, igx_ctx *ctx, const GbArgs &a) {
     b.vcount[0] = 1;
     b.hascond[0] = 0;
     b.valid = a.valid;
-    b.krec = st->krec;
-    b.vrec = st->vrec;
-    b.krec_len = st->krec_len;
-    b.krec_total = (uint32_t)(st->nslots * st->krec_len);
-    b.vrec_words = st->vrec_len / 8;
-    b.vrec_total = st->nslots * st->vrec_len < (1ull << 32) ? (uint32_t)(st->nslots * st->vrec_len) : 0u;
-    b.err = st->err;
-    b.occ = st->occ;
-    b.occb = st->occb;
-    b.ep = st->ep;
-    b.gen = reinterpret_cast<uint64_t *>(st->err) + GEN_WORD;
-    b.sshift = 64 - st->sbits;
-    b.rmask = (1ull << st->rbits) - 1;
-    b.max_probe = 1u << st->rbits;
+    bind_records(st, b);
     b.dbg = 0;
     b.sm = 0;
     b.direct = 0;
@@ -2897,7 +2865,6 @@ static int seeds_compute_static(igx_table *t, igx_ctx *ctx, const GbArgs &a) {
     b.seeds = nullptr;
     b.seed_gep = nullptr;
     b.nseeds = 0;
-    b.dbg_cnt = st->dbg_cnt;
     st->rows_fed = S;
     st->fin_since_update = false;
     st->interval_direct = st->interval_part = false;
@@ -2994,20 +2961,12 @@ extern "C" int igx_groupby_update(igx_table *t, const igx_col *cols, uint32_t nc
     return igx_groupby_update_ex(t, cols, ncols, key_cols, preds, npreds, nullptr, IGX_NO_COL, nrows, base_idx);
 }
 
-extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t ncols, const uint32_t *key_cols,
-                                     const igx_pred *preds, uint32_t npreds, const uint8_t *valid, uint32_t idx_col,
-                                     uint64_t nrows, uint64_t base_idx) {
-    if (!t) return IGX_EINVAL;
+// ---- one update's GbArgs, piece by piece (igx_groupby_update_ex calls them in this order) ----
+
+// the key columns.  Key column 0 (a.kcol[0]) doubles as the dummy column: any readable dword
+// for loads whose result is discarded (padding words, COUNT, no cond, unused predicate slots)
+static int plan_keys(igx_table *t, const igx_col *cols, uint32_t ncols, const uint32_t *key_cols, GbArgs &a) {
     igx_ctx *ctx = t->ctx;
-    if (nrows == 0) return IGX_OK;
-    if (!cols || !key_cols) return igx_fail(ctx, IGX_EINVAL, "groupby_update: null columns");
-    if (nrows >= (1ull << 32)) return igx_fail(ctx, IGX_EINVAL, "groupby_update: more than 2^32 rows in one call");
-    if (base_idx + nrows >= READY_IDX)   // `ready` carries first_ins + 1 (a kept key's: index + 2) in 48 bits
-        return igx_fail(ctx, IGX_EINVAL, "groupby_update: event indices reach 2^48 (rebase the interval's indices)");
-    t->rows_fed += nrows;
-    t->fin_since_update = false;
-    t->fin_current = false;
-    GbArgs a{};
     uint32_t w = 0;
     for (uint32_t k = 0; k < t->nkeys; ++k) {
         const uint32_t ci = key_cols[k];
@@ -3031,23 +2990,27 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
             a.kbytes[w] = odd ? std::min<uint32_t>(4, c.width - 4 * j) : 0;
         }
     }
-    // any readable dword for loads whose result is discarded (padding words, COUNT, no cond)
-    const uint8_t *dummy = static_cast<const uint8_t *>(cols[key_cols[0]].ptr);
     for (; w < KWMAX; ++w) {
-        a.kptr[w] = dummy;
+        a.kptr[w] = a.kcol[0];
         a.kwidth[w] = 0;
         a.koff[w] = 0;
         a.kmask[w] = 0;
     }
-    // Scalar columns other than keys (aggregate values and conditions, predicates, guards, the
-    // nil mask) are read as the aligned dwords that hold each row, formed from the column's
-    // base: a base off a 4-byte boundary would make them misaligned loads that run up to three
-    // bytes past the column's last 4-byte block.
-    auto misaligned = [](const igx_col &c) {
-        return (reinterpret_cast<uintptr_t>(c.ptr) & (c.width == 8 ? 7u : 3u)) != 0;
-    };
-    if (valid && (reinterpret_cast<uintptr_t>(valid) & 3u))
-        return igx_fail(ctx, IGX_EINVAL, "groupby_update: valid mask misaligned");
+    return IGX_OK;
+}
+
+// Scalar columns other than keys (aggregate values and conditions, predicates, guards, the
+// nil mask) are read as the aligned dwords that hold each row, formed from the column's
+// base: a base off a 4-byte boundary would make them misaligned loads that run up to three
+// bytes past the column's last 4-byte block.
+static bool misaligned(const igx_col &c) {
+    return (reinterpret_cast<uintptr_t>(c.ptr) & (c.width == 8 ? 7u : 3u)) != 0;
+}
+
+// the aggregates' value and condition columns, and which of them share a load
+static int plan_aggs(igx_table *t, const igx_col *cols, uint32_t ncols, GbArgs &a) {
+    igx_ctx *ctx = t->ctx;
+    const uint8_t *dummy = a.kcol[0];
     a.naggs = t->naggs;
     for (uint32_t x = t->naggs; x < AMAX; ++x) {   // unused slots are still loaded (issue_row)
         a.vptr[x] = a.cptr[x] = dummy;
@@ -3063,7 +3026,7 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
             a.vptr[x] = static_cast<const uint8_t *>(cols[g.col].ptr);
             a.vwidth[x] = cols[g.col].width;
             a.vsign[x] = cols[g.col].kind == IGX_KIND_INT;
-            if (a.vwidth[x] != 1 && a.vwidth[x] != 2 && a.vwidth[x] != 4 && a.vwidth[x] != 8)
+            if (!igx_scalar_width(a.vwidth[x]))
                 return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: agg width %u", a.vwidth[x]);
             if (cols[g.col].kind == IGX_KIND_FLOAT)
                 return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: float sums are not supported");
@@ -3080,7 +3043,7 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
         if (g.cond_col != IGX_NO_COL) {
             if (g.cond_col >= ncols) return igx_fail(ctx, IGX_EINVAL, "groupby_update: cond column out of range");
             const uint32_t cw = cols[g.cond_col].width;
-            if (cw != 1 && cw != 2 && cw != 4 && cw != 8)
+            if (!igx_scalar_width(cw))
                 return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: condition width %u", cw);
             if (misaligned(cols[g.cond_col]))
                 return igx_fail(ctx, IGX_EINVAL, "groupby_update: condition column of aggregate %u misaligned", x);
@@ -3111,9 +3074,16 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
         a.vhioff[x] = a.vload[x] && a.vwidth[x] == 8 ? 4 : 0;
         a.chioff[x] = a.cload[x] && a.cwidth[x] == 8 ? 4 : 0;
     }
-    // Up to PMAX scalar comparisons (and IN sets) are fused into the kernel; any others --
-    // more predicates, regex or string rules -- are AND-ed into a row mask first by a scan
-    // with the filter's predicate evaluator (k_common.h), which then masks rows like `valid`.
+    return IGX_OK;
+}
+
+// Up to PMAX scalar comparisons (and IN sets) are fused into the kernel; any others --
+// more predicates, regex or string rules -- are AND-ed into a row mask first by a scan
+// with the filter's predicate evaluator (k_common.h), which then masks rows like `valid`.
+static int plan_preds(igx_table *t, const igx_col *cols, uint32_t ncols, const igx_pred *preds, uint32_t npreds,
+                      const uint8_t *valid, uint64_t nrows, GbArgs &a) {
+    igx_ctx *ctx = t->ctx;
+    const uint8_t *dummy = a.kcol[0];
     std::vector<igx_pred> fused, masked;
     // a guard is fused when it is the condition column of an aggregate (whose raw value the
     // kernel holds anyway): that aggregate's index, else AMAX
@@ -3123,11 +3093,12 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
             if (a.hascond[x] && a.cptr[x] == static_cast<const uint8_t *>(g.ptr) && a.cwidth[x] == g.width) return x;
         return AMAX;
     };
+    // a scalar comparison, or on such a column an IN set (or a comparison number past it, which
+    // the fused plan below rejects by that number), unless a guard keeps it out
     auto fusable = [&](const igx_pred &q) {
         const igx_col &c = cols[q.col];
-        return !(q.cmp == IGX_CMP_REGEX || c.kind == IGX_KIND_BYTES || c.kind == IGX_KIND_BOOL ||
-                 c.kind == IGX_KIND_OTHER || (c.width != 1 && c.width != 2 && c.width != 4 && c.width != 8) ||
-                 (c.kind == IGX_KIND_FLOAT && c.width < 4) || (q.guard_len && guard_agg(q) == AMAX));
+        return igx_scalar_cmp(c.kind, c.width, q.cmp >= IGX_CMP_IN ? (uint32_t)IGX_CMP_EQ : q.cmp) &&
+               !(q.guard_len && guard_agg(q) == AMAX);
     };
     for (uint32_t p = 0; p < npreds; ++p) {
         if (preds[p].col >= ncols) return igx_fail(ctx, IGX_EINVAL, "groupby_update: predicate column out of range");
@@ -3189,10 +3160,7 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
         a.pkind[p] = c.kind;
         a.pcmp[p] = q.cmp;
         a.pneg[p] = q.negate;
-        uint64_t r = 0;
-        const uint32_t nb = q.cmp == IGX_CMP_IN ? q.ref_len : c.width;
-        for (uint32_t b = 0; b < nb; ++b) r |= (uint64_t)q.ref[b] << (8 * b);
-        a.pref[p] = r;
+        a.pref[p] = igx_pack_ref(q.ref, q.cmp == IGX_CMP_IN ? q.ref_len : c.width);
         a.pldw[p] = c.width;
         a.pshare[p] = a.pguard[p] = AMAX;
         for (uint32_t x = 0; x < t->naggs; ++x)   // the value column of an aggregate: reuse its load
@@ -3205,7 +3173,7 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
             a.pguard[p] = guard_agg(q);
             a.gptr[p] = static_cast<const uint8_t *>(cols[q.guard_col].ptr);
             a.gwidth[p] = q.guard_len;
-            a.gref[p] = igx_guard_ref(q);
+            a.gref[p] = igx_pack_ref(q.guard_ref, q.guard_len);
         }
     }
     for (uint32_t p = npreds; p < PMAX; ++p) {
@@ -3218,6 +3186,13 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
     a.valid = valid;
     a.validp = valid ? valid : dummy;
     a.validw = valid ? 1 : 0;
+    return IGX_OK;
+}
+
+// the rows' indices, the table's records and the per-call knobs
+static int bind_table(igx_table *t, const igx_col *cols, uint32_t ncols, uint32_t idx_col, uint64_t nrows,
+                      uint64_t base_idx, GbArgs &a) {
+    igx_ctx *ctx = t->ctx;
     a.fidx = nullptr;
     if (idx_col != IGX_NO_COL) {
         if (idx_col >= ncols || cols[idx_col].width != 8)
@@ -3226,20 +3201,7 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
     }
     a.n = nrows;
     a.base_idx = base_idx;
-    a.krec = t->krec;
-    a.vrec = t->vrec;
-    a.krec_len = t->krec_len;
-    a.krec_total = (uint32_t)(t->nslots * t->krec_len);
-    a.vrec_words = t->vrec_len / 8;
-    a.vrec_total = t->nslots * t->vrec_len < (1ull << 32) ? (uint32_t)(t->nslots * t->vrec_len) : 0u;
-    a.err = t->err;
-    a.occ = t->occ;
-    a.occb = t->occb;
-    a.ep = t->ep;
-    a.gen = reinterpret_cast<uint64_t *>(t->err) + GEN_WORD;
-    a.sshift = 64 - t->sbits;
-    a.rmask = (1ull << t->rbits) - 1;
-    a.max_probe = 1u << t->rbits;
+    bind_records(t, a);
     if (const char *d = std::getenv("IGX_GB_DEBUG")) a.dbg = (uint32_t)std::strtoul(d, nullptr, 0);
     // one loader wave fewer (one prober more) after intervals that missed the cache on more
     // than MORE_PROBERS_ON_PM / 1000 of their rows (until one falls below MORE_PROBERS_OFF_PM)
@@ -3255,13 +3217,14 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
     if (const char *d = std::getenv("IGX_GB_PROBER")) a.sm = std::strtoul(d, nullptr, 0) ? 1u : 0u;   // ablation
     if (const char *d = std::getenv("IGX_GB_ADMIT"))   // ablation: 0 first-miss admission, k: on the (k+1)-th
         a.admit_mask = std::min<uint32_t>(3u, (uint32_t)std::strtoul(d, nullptr, 0));
-    a.dbg_cnt = t->dbg_cnt;
-    const uint64_t want = (nrows + GTB - 1) / GTB;
-    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)ctx->num_cus));
-    const uint32_t *kw = t->key_widths;
-    // the interval's form is fixed by its first update (the LDS-miss count that drives AUTO
-    // is only meaningful for a whole interval of the cached form)
-    if (t->rows_fed == nrows) {
+    return IGX_OK;
+}
+
+// the interval's form is fixed by its first update (the LDS-miss count that drives AUTO
+// is only meaningful for a whole interval of the cached form)
+static int choose_form(igx_table *t, const GbArgs &a) {
+    igx_ctx *ctx = t->ctx;
+    if (t->rows_fed == a.n) {
         t->interval_direct = t->mode == IGX_GB_DIRECT;
         t->interval_part = t->mode == IGX_GB_PART || (t->mode == IGX_GB_AUTO && t->direct_left > 0);
         t->interval_probe = false;
@@ -3276,38 +3239,69 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
         IGX_HIP(ctx, hipGetLastError());
         t->gen_planned = false;
     }
-    int rc = IGX_OK;
-#ifdef IGX_DEV_FAST   // development builds: the bench's key layouts only (fast kernel iteration)
-    if (layout_is<TcpKey>(kw, t->nkeys)) rc = launch_form<TcpKey>(t, ctx, a, blocks);
-    else if (layout_is<FileKey>(kw, t->nkeys)) rc = launch_form<FileKey>(t, ctx, a, blocks);
-    else if (layout_is<NetPolicyKey>(kw, t->nkeys)) rc = launch_form<NetPolicyKey>(t, ctx, a, blocks);
-    else return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: layout not in this development build");
-#else
+    return IGX_OK;
+}
+
+// one update in the interval's form, over the table's key layout
+static int launch_layout(igx_table *t, GbArgs &a) {
+    igx_ctx *ctx = t->ctx;
+    const uint64_t want = (a.n + GTB - 1) / GTB;
+    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)ctx->num_cus));
+    const uint32_t *kw = t->key_widths;
+#ifndef IGX_DEV_FAST
     if (t->generic) {
         switch (t->kw_rec) {
-        case 2: rc = launch_form<GenericLayout<2>>(t, ctx, a, blocks); break;
-        case 4: rc = launch_form<GenericLayout<4>>(t, ctx, a, blocks); break;
-        case 6: rc = launch_form<GenericLayout<6>>(t, ctx, a, blocks); break;
-        case 8: rc = launch_form<GenericLayout<8>>(t, ctx, a, blocks); break;
-        case 12: rc = launch_form<GenericLayout<12>>(t, ctx, a, blocks); break;
-        case 18: rc = launch_form<GenericLayout<18>>(t, ctx, a, blocks); break;
-        case 24: rc = launch_form<GenericLayout<24>>(t, ctx, a, blocks); break;
-        case 32: rc = launch_form<GenericLayout<32>>(t, ctx, a, blocks); break;
+        case 2: return launch_form<GenericLayout<2>>(t, ctx, a, blocks);
+        case 4: return launch_form<GenericLayout<4>>(t, ctx, a, blocks);
+        case 6: return launch_form<GenericLayout<6>>(t, ctx, a, blocks);
+        case 8: return launch_form<GenericLayout<8>>(t, ctx, a, blocks);
+        case 12: return launch_form<GenericLayout<12>>(t, ctx, a, blocks);
+        case 18: return launch_form<GenericLayout<18>>(t, ctx, a, blocks);
+        case 24: return launch_form<GenericLayout<24>>(t, ctx, a, blocks);
+        case 32: return launch_form<GenericLayout<32>>(t, ctx, a, blocks);
         default: return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: no kernel for %u key words", t->kw_rec);
         }
-    } else if (layout_is<TcpKey>(kw, t->nkeys)) rc = launch_form<TcpKey>(t, ctx, a, blocks);
-    else if (layout_is<FileKey>(kw, t->nkeys)) rc = launch_form<FileKey>(t, ctx, a, blocks);
-    else if (layout_is<NetPolicyKey>(kw, t->nkeys))
-        rc = launch_form<NetPolicyKey>(t, ctx, a, blocks);
-    else if (layout_is<BioKey>(kw, t->nkeys)) rc = launch_form<BioKey>(t, ctx, a, blocks);
-    else if (t->nkeys == 1 && kw[0] == 1) rc = launch_form<StaticLayout<1>>(t, ctx, a, blocks);
-    else if (t->nkeys == 1 && kw[0] == 2) rc = launch_form<StaticLayout<2>>(t, ctx, a, blocks);
-    else if (t->nkeys == 1 && kw[0] == 4) rc = launch_form<StaticLayout<4>>(t, ctx, a, blocks);
-    else if (t->nkeys == 1 && kw[0] == 8) rc = launch_form<StaticLayout<8>>(t, ctx, a, blocks);
-    else if (t->nkeys == 1 && kw[0] == 16) rc = launch_form<StaticLayout<16>>(t, ctx, a, blocks);
-    else return igx_fail(ctx, IGX_EINVAL, "groupby_update: internal layout mismatch");
+    }
 #endif
+    if (layout_is<TcpKey>(kw, t->nkeys)) return launch_form<TcpKey>(t, ctx, a, blocks);
+    if (layout_is<FileKey>(kw, t->nkeys)) return launch_form<FileKey>(t, ctx, a, blocks);
+    if (layout_is<NetPolicyKey>(kw, t->nkeys)) return launch_form<NetPolicyKey>(t, ctx, a, blocks);
+#ifdef IGX_DEV_FAST   // development builds: the bench's key layouts only (fast kernel iteration)
+    return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: layout not in this development build");
+#else
+    if (layout_is<BioKey>(kw, t->nkeys)) return launch_form<BioKey>(t, ctx, a, blocks);
+    if (t->nkeys == 1 && kw[0] == 1) return launch_form<StaticLayout<1>>(t, ctx, a, blocks);
+    if (t->nkeys == 1 && kw[0] == 2) return launch_form<StaticLayout<2>>(t, ctx, a, blocks);
+    if (t->nkeys == 1 && kw[0] == 4) return launch_form<StaticLayout<4>>(t, ctx, a, blocks);
+    if (t->nkeys == 1 && kw[0] == 8) return launch_form<StaticLayout<8>>(t, ctx, a, blocks);
+    if (t->nkeys == 1 && kw[0] == 16) return launch_form<StaticLayout<16>>(t, ctx, a, blocks);
+    return igx_fail(ctx, IGX_EINVAL, "groupby_update: internal layout mismatch");
+#endif
+}
+
+extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t ncols, const uint32_t *key_cols,
+                                     const igx_pred *preds, uint32_t npreds, const uint8_t *valid, uint32_t idx_col,
+                                     uint64_t nrows, uint64_t base_idx) {
+    if (!t) return IGX_EINVAL;
+    igx_ctx *ctx = t->ctx;
+    if (nrows == 0) return IGX_OK;
+    if (!cols || !key_cols) return igx_fail(ctx, IGX_EINVAL, "groupby_update: null columns");
+    if (nrows >= (1ull << 32)) return igx_fail(ctx, IGX_EINVAL, "groupby_update: more than 2^32 rows in one call");
+    if (base_idx + nrows >= READY_IDX)   // `ready` carries first_ins + 1 (a kept key's: index + 2) in 48 bits
+        return igx_fail(ctx, IGX_EINVAL, "groupby_update: event indices reach 2^48 (rebase the interval's indices)");
+    t->rows_fed += nrows;
+    t->fin_since_update = false;
+    t->fin_current = false;
+    GbArgs a{};
+    int rc = plan_keys(t, cols, ncols, key_cols, a);
     if (rc) return rc;
+    if (valid && (reinterpret_cast<uintptr_t>(valid) & 3u))
+        return igx_fail(ctx, IGX_EINVAL, "groupby_update: valid mask misaligned");
+    if ((rc = plan_aggs(t, cols, ncols, a))) return rc;
+    if ((rc = plan_preds(t, cols, ncols, preds, npreds, valid, nrows, a))) return rc;
+    if ((rc = bind_table(t, cols, ncols, idx_col, nrows, base_idx, a))) return rc;
+    if ((rc = choose_form(t, a))) return rc;
+    if ((rc = launch_layout(t, a))) return rc;
     IGX_HIP(ctx, hipGetLastError());
     return IGX_OK;
 }

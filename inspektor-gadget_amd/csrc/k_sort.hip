@@ -394,7 +394,7 @@ __global__ __launch_bounds__(TB) void k_compose(ComposeArgs a, uint32_t *__restr
             }
         } else {
             const bool sgn = a.kind[k] == IGX_KIND_INT;
-            uint64_t v = ld_scalar(p, a.width[k], 0, false);
+            uint64_t v = ld_scalar(p, a.width[k], 0);
             if (sgn) v ^= 1ull << (8 * a.width[k] - 1);
             if (nw == 1) {
                 words[w * a.stride + i] = (uint32_t)v ^ inv;

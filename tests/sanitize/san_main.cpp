@@ -1,11 +1,14 @@
 // Host-side sanitizer driver (ASan + UBSan build, tests/sanitize/Makefile): runs the host
 // parsers of libigx -- igx_filter_parse (filter.GetFilterFromString), igx_regex_compile_blob
 // (the `~` rule's DFA compiler) and igx_sort_prepare (sort.Prepare) -- over a corpus of
-// inputs, plus seeded random regex patterns and filter strings.  Test infrastructure only.
+// inputs, plus seeded random regex patterns and filter strings -- and the kernels' scalar
+// predicate core (k_pred.h), which is plain C++ on the host.  Test infrastructure only.
 //
 // corpus lines:  F <tab> filter string     (against the schema below)
 //                R <tab> regex pattern
 //                S <tab> sortBy entries separated by ','
+//                P <tab> kind width cmp negate value ref cnt expected   (pred_scalar; value and
+//                        ref are zero-extended hex u64, cnt the IN set's size, expected 0 / 1)
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -13,6 +16,7 @@
 #include <vector>
 
 #include "../../include/igx.h"
+#include "../../inspektor-gadget_amd/csrc/k_pred.h"
 
 namespace {
 
@@ -72,6 +76,15 @@ int run_sort(const std::string &s) {
     return igx_sort_prepare(kSchema, kN, ptrs.data(), (uint32_t)ptrs.size(), out.data(), &n, &bad);
 }
 
+// 0: pred_scalar gives the expected bit
+int run_pred(const std::string &s) {
+    unsigned kind, width, cmp, neg, cnt, want;
+    unsigned long long v, ref;
+    if (std::sscanf(s.c_str(), "%u %u %u %u %llx %llx %u %u", &kind, &width, &cmp, &neg, &v, &ref, &cnt, &want) != 8)
+        return 1;
+    return pred_scalar(v, ref, width, kind, cmp, neg, cnt) == (want != 0) ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -94,6 +107,10 @@ int main(int argc, char **argv) {
             if (line[0] == 'F') rc = run_filter(arg);
             else if (line[0] == 'R') rc = run_regex(arg);
             else if (line[0] == 'S') rc = run_sort(arg);
+            else if (line[0] == 'P' && (rc = run_pred(arg))) {
+                std::fprintf(stderr, "predicate mismatch: %s\n", line.c_str());
+                return 1;
+            }
             ++lines;
             ok += rc == 0;
         }
