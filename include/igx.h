@@ -300,10 +300,26 @@ typedef struct {
     uint32_t desc;   /* '-' prefix */
 } igx_tsortkey;
 
-/* capacity = maximum number of distinct groups.  key_widths: byte width of each key
- * column, any width (packed, each padded to a multiple of 4; at most IGX_MAX_KEY_BYTES
- * padded bytes in all).  The table's key records must stay below 4 GiB (S >= 2 x capacity
- * slots of 32..256 B: about 16M groups for the 72-B ip_key_t), IGX_ENOTSUP otherwise. */
+/* capacity = maximum number of distinct groups (at most 2^28, the only limit on it).
+ * key_widths: byte width of each key column, any width (packed, each padded to a multiple of 4;
+ * at most IGX_MAX_KEY_BYTES padded bytes in all).
+ * Memory: S slots, S the power of two >= 2 x capacity (>= 1024).  A slot takes a key record
+ * (igx_table_view.key_stride: 32..256 B, the padded key + 16 B rounded up to a power of two --
+ * 128 B for the 72-B ip_key_t, 64 B for top file's key), a value record (val_stride: 8 + 8 x
+ * naggs B rounded up to a power of two) and 5 1/8 B of slot list and occupancy maps; the
+ * partitioned form adds scratch per update (igx_groupby_set_mode).  Device memory that cannot
+ * be had is IGX_ENOMEM and nothing stays allocated.
+ * A table whose key records reach 4 GiB (S x key_stride >= 2^32) is *wide*.  Up to there
+ * (8.39M ip_key_t groups, 4.19M groups of a 128-byte key, 16.7M of top file's) a table is
+ * narrow and runs as it always did.  A wide table addresses its key records with per-lane
+ * 64-bit addresses in place of one buffer descriptor; it runs the direct and the partitioned
+ * form, and IGX_GB_AUTO plans every interval of it partitioned (such a table is the
+ * high-cardinality case that form is for; no interval is measured in the cached form, so keys
+ * are not kept across its intervals either).  The cached form is not offered on a wide table
+ * yet (igx_groupby_set_mode).  Everything that reads a table -- finalize, sort, gather,
+ * select_ge, lookup, igx_partition_groups -- works on both kinds alike, and results are
+ * identical.  IGX_GB_WIDE=1 in the environment at create gives a narrow-sized table the wide
+ * kernels (A/B measurements and tests). */
 int igx_groupby_create(igx_ctx *ctx, const uint32_t *key_widths, uint32_t nkeys,
                        const igx_agg *aggs, uint32_t naggs, uint64_t capacity,
                        igx_table **out);
@@ -427,7 +443,12 @@ int igx_groupby_reset(igx_table *t);
  *   IGX_GB_AUTO    (default) cached; an interval in which more than 90% of the rows missed
  *                  the cache switches the next 16 intervals to partitioned, then measures
  *                  again.
- * The mode of an interval is fixed by its first update. */
+ * The mode of an interval is fixed by its first update.
+ * On a wide table (igx_groupby_create) IGX_GB_AUTO runs every interval partitioned, and
+ * IGX_GB_CACHED is refused: IGX_ENOTSUP, the message says why, the table keeps its mode and
+ * goes on working (nor do IGX_GB_MODE=1 or IGX_GB_DEBUG force it).  The cached kernel's probers
+ * address key records through a buffer descriptor; a wide prober within its register budget is
+ * the follow-up. */
 enum igx_gb_mode { IGX_GB_AUTO = 0, IGX_GB_CACHED = 1, IGX_GB_DIRECT = 2, IGX_GB_PART = 3 };
 int igx_groupby_set_mode(igx_table *t, uint32_t mode);
 /* SortStats over the table's groups (same order as igx_sort_perm with pos = first_idx);

@@ -169,7 +169,7 @@ struct GbArgs {
     uint8_t *krec;          // key records
     uint64_t *vrec;         // value records
     uint32_t krec_len;      // KR
-    uint32_t krec_total;    // S x KR (< 2^32)
+    uint32_t krec_total;    // S x KR of a narrow table (< 2^32); 0 on a wide one (no descriptor reaches it)
     uint32_t vrec_words;    // VR / 8
     uint32_t vrec_total;    // S x VR when below 4 GiB (16-B buffer stores of a claim), else 0
     uint32_t *err;
@@ -344,10 +344,63 @@ __device__ __forceinline__ void load_rec(__amdgpu_buffer_rsrc_t rs, uint32_t off
 template <int KW>
 constexpr int probe_quads() { return (int)((koff_of(KW) + 16 + 15) / 16); }   // key, tag, ready
 
-// the home slot's record, issued early so its round trip overlaps other work
-template <int KW>
-__device__ __forceinline__ void probe_issue(const GbArgs &a, uint64_t h, uint32_t (&d)[probe_quads<KW>() * 4]) {
-    load_rec<probe_quads<KW>()>(rec_rsrc(a), (uint32_t)(home_slot(a, h) * a.krec_len), d);
+// Record addressing.  A narrow table (S x KR < 4 GiB) addresses its key records
+// through one raw buffer descriptor and a 32-bit byte offset.  A wide table (WIDE = true: S x KR
+// >= 4 GiB, or IGX_GB_WIDE=1) addresses them per lane, krec + slot * KR in 64 bits, with the
+// global forms of the same 16-byte write-through (sc1) loads and stores.  Those have no builtin,
+// so they are inline asm, which the compiler does not count: a wide load's registers hold its
+// data only after probe_wait.  The policy is a template parameter: the narrow instances carry
+// none of the wide code.
+template <int KW, bool WIDE = false>
+using probe_regs = std::conditional_t<WIDE, u4v[probe_quads<KW>()], uint32_t[probe_quads<KW>() * 4]>;
+
+// word i (a compile-time index) of a probed record
+template <bool WIDE, class D>
+__device__ __forceinline__ uint32_t rec_word(const D &d, int i) {
+    if constexpr (WIDE) return d[i / 4][i % 4];
+    else return d[i];
+}
+
+template <int I>
+__device__ __forceinline__ void wide_load_quad(const uint8_t *p, u4v &q) {
+    asm volatile("global_load_dwordx4 %0, %1, off offset:%2 sc1" : "=v"(q) : "v"(p), "i"(16 * I) : "memory");
+}
+template <int NQ, size_t... I>
+__device__ __forceinline__ void wide_load_quads(const uint8_t *p, u4v (&d)[NQ], std::index_sequence<I...>) {
+    (wide_load_quad<(int)I>(p, d[I]), ...);
+}
+// issues the loads of a record's first NQ quads; d is undefined until wide_wait_rec<NQ>(d)
+template <int NQ>
+__device__ __forceinline__ void wide_issue_rec(const uint8_t *p, u4v (&d)[NQ]) {
+    wide_load_quads<NQ>(p, d, std::make_index_sequence<NQ>{});
+}
+// the wait names every destination: no use of d is scheduled above it
+template <int NQ>
+__device__ __forceinline__ void wide_wait_rec(u4v (&d)[NQ]) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(d[0]) : : "memory");
+#pragma unroll
+    for (int i = 1; i < NQ; ++i) asm volatile("" : "+v"(d[i]));
+}
+template <int NQ>
+__device__ __forceinline__ void wide_load_rec(const uint8_t *p, u4v (&d)[NQ]) {
+    wide_issue_rec<NQ>(p, d);
+    wide_wait_rec<NQ>(d);
+}
+// 16 bytes, written through; the trailing nop keeps the data registers until the store has read them
+__device__ __forceinline__ void wide_store_quad(uint8_t *p, u4v q) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(q) : "memory");
+}
+
+// the home slot's record, issued early so its round trip overlaps other work (wide: probe_wait
+// before find_or_insert)
+template <int KW, bool WIDE = false>
+__device__ __forceinline__ void probe_issue(const GbArgs &a, uint64_t h, probe_regs<KW, WIDE> &d) {
+    if constexpr (WIDE) wide_issue_rec<probe_quads<KW>()>(a.krec + home_slot(a, h) * a.krec_len, d);
+    else load_rec<probe_quads<KW>()>(rec_rsrc(a), (uint32_t)(home_slot(a, h) * a.krec_len), d);
+}
+template <int KW, bool WIDE = false>
+__device__ __forceinline__ void probe_wait(probe_regs<KW, WIDE> &d) {
+    if constexpr (WIDE) wide_wait_rec<probe_quads<KW>()>(d);
 }
 
 // A claimer's value record: first = its event index, aggregate x = vinit[x] (the claiming
@@ -388,22 +441,32 @@ __device__ __forceinline__ void vrec_init(const GbArgs &a, uint64_t s, uint64_t 
 // d holds the home slot's record (probe_issue).  vinit: the event's aggregate values, written
 // into the value record when this call claims the slot (claimed = true; the caller then adds
 // them nowhere else).
-template <int KW, bool SET_OCC, int NV>
+template <int KW, bool SET_OCC, int NV, bool WIDE = false>
 __device__ __forceinline__ uint32_t find_or_insert(const GbArgs &a, const uint32_t (&k)[KW], uint64_t h,
                                                    uint64_t gidx, uint64_t &first_ins,
-                                                   uint32_t (&d)[probe_quads<KW>() * 4],
+                                                   probe_regs<KW, WIDE> &d,
                                                    const uint64_t (&vinit)[NV], bool &claimed) {
     constexpr uint32_t KOFF = koff_of(KW);
     constexpr int NQ = probe_quads<KW>();
     const uint64_t tag = (h & ~EP_MAX) | a.ep;
-    const __amdgpu_buffer_rsrc_t rs = rec_rsrc(a);
+    [[maybe_unused]] const auto rs = [&] {   // narrow: the records' descriptor
+        if constexpr (WIDE) return 0;
+        else return rec_rsrc(a);
+    }();
+    // the record at byte offset off (narrow) / at r (wide), complete when this returns
+    auto reload = [&](uint32_t off, const uint8_t *r) {
+        if constexpr (WIDE) wide_load_rec<NQ>(r, d);
+        else load_rec<NQ>(rs, off, d);
+    };
     uint64_t s = home_slot(a, h);
     for (uint32_t probe = 0; probe < a.max_probe; ++probe) {
-        const uint32_t off = (uint32_t)(s * a.krec_len);
-        if (probe) load_rec<NQ>(rs, off, d);
-        uint8_t *r = a.krec + off;
-        uint64_t t = (uint64_t)d[KOFF / 4] | ((uint64_t)d[KOFF / 4 + 1] << 32);
-        uint64_t ready = (uint64_t)d[KOFF / 4 + 2] | ((uint64_t)d[KOFF / 4 + 3] << 32);
+        const uint32_t off = (uint32_t)(s * a.krec_len);   // narrow only
+        uint8_t *r;
+        if constexpr (WIDE) r = a.krec + s * a.krec_len;
+        else r = a.krec + off;
+        if (probe) reload(off, r);
+        uint64_t t = (uint64_t)rec_word<WIDE>(d, KOFF / 4) | ((uint64_t)rec_word<WIDE>(d, KOFF / 4 + 1) << 32);
+        uint64_t ready = (uint64_t)rec_word<WIDE>(d, KOFF / 4 + 2) | ((uint64_t)rec_word<WIDE>(d, KOFF / 4 + 3) << 32);
         if ((t & EP_MAX) != a.ep) {   // empty in this interval (never claimed, or an older epoch's)
             if (gidx >= READY_IDX) {   // an index column value that `ready` cannot carry
                 atomicOr(a.err, 8u);
@@ -417,7 +480,8 @@ __device__ __forceinline__ uint32_t find_or_insert(const GbArgs &a, const uint32
                 for (int w = 0; w < KW; w += 4) {
                     if (w + 3 < KW) {
                         const u4v q = {k[w], k[w + 1], k[w + 2], k[w + 3]};
-                        __builtin_amdgcn_raw_buffer_store_b128(q, rs, off + 4 * w, 0, 16 /* sc1 */);
+                        if constexpr (WIDE) wide_store_quad(r + 4 * w, q);
+                        else __builtin_amdgcn_raw_buffer_store_b128(q, rs, off + 4 * w, 0, 16 /* sc1 */);
                     } else if (w + 1 < KW) {
                         st_agent(reinterpret_cast<uint64_t *>(r + 4 * w), (uint64_t)k[w] | ((uint64_t)k[w + 1] << 32));
                         if (w + 2 < KW) st_agent(reinterpret_cast<uint32_t *>(r + 4 * w + 8), k[w + 2]);
@@ -448,22 +512,22 @@ __device__ __forceinline__ uint32_t find_or_insert(const GbArgs &a, const uint32
                         return SLOT_OVF;
                     }
                 }
-                load_rec<NQ>(rs, off, d);
+                reload(off, r);
             }
             bool eq = true;
 #pragma unroll
-            for (int w = 0; w < KW; ++w) eq = eq && (d[w] == k[w]);
+            for (int w = 0; w < KW; ++w) eq = eq && (rec_word<WIDE>(d, w) == k[w]);
             if (!eq) {
                 // The quads of one snapshot are separate loads: `ready` may have been sampled
                 // after the key quads, so a tag hit with a key mismatch is re-read once, now
                 // ordered after the ready observation (genuine 64-bit tag collisions are rare).
-                load_rec<NQ>(rs, off, d);
+                reload(off, r);
                 eq = true;
 #pragma unroll
-                for (int w = 0; w < KW; ++w) eq = eq && (d[w] == k[w]);
+                for (int w = 0; w < KW; ++w) eq = eq && (rec_word<WIDE>(d, w) == k[w]);
             }
             if (eq) {
-                first_ins = (((uint64_t)d[KOFF / 4 + 2] | ((uint64_t)d[KOFF / 4 + 3] << 32)) & READY_IDX) - 1;
+                first_ins = (((uint64_t)rec_word<WIDE>(d, KOFF / 4 + 2) | ((uint64_t)rec_word<WIDE>(d, KOFF / 4 + 3) << 32)) & READY_IDX) - 1;
                 return (uint32_t)s;
             }
         }
@@ -1708,7 +1772,9 @@ __global__ __launch_bounds__(256) void k_gb_seeds(GbArgs a, const uint8_t *__res
 // the atomicMin on `first` is then rare) and resolves each one itself: probe, compare,
 // claim, atomics.  The throughput is the chip's random-access rate (~45-50 G probes/s over
 // a 1 GiB table, tools/micro/randacc.hip); occupancy, not a pipeline, hides the latency.
-template <class L, int NA>
+// WIDE: the table's record addressing (probe_issue); the wide instance keeps the shape -- its
+// probes' loads are in flight together and probe_wait retires them before the first resolve.
+template <class L, int NA, bool WIDE = false>
 __global__ __launch_bounds__(256) void k_groupby_direct(GbArgs a) {
     constexpr int KW = L::KW;
     constexpr int U = IGX_GB_DIRECT_U;   // rows in flight per lane: all rows' loads, then all probes
@@ -1723,13 +1789,21 @@ __global__ __launch_bounds__(256) void k_groupby_direct(GbArgs a) {
         uint32_t k[U][KW];
         uint64_t v[U][NA], h[U];
         bool ok[U];
-        uint32_t d[U][probe_quads<KW>() * 4];
+        probe_regs<KW, WIDE> d[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint64_t row = row0 + u * stride;
             ok[u] = row < a.n && decode_row<L, NA>(a, row, R[u], k[u], v[u]);
             h[u] = hash_key<KW>(k[u]);
-            if (ok[u]) probe_issue<KW>(a, h[u], d[u]);
+            if constexpr (WIDE) {   // every lane loads (a dropped row: slot 0), so every d is defined
+                probe_issue<KW, true>(a, ok[u] ? h[u] : 0ull, d[u]);
+            } else {
+                if (ok[u]) probe_issue<KW>(a, h[u], d[u]);
+            }
+        }
+        if constexpr (WIDE) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) probe_wait<KW, true>(d[u]);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -1739,7 +1813,7 @@ __global__ __launch_bounds__(256) void k_groupby_direct(GbArgs a) {
             bool claimed = false;
             // no occupancy bit: finalize rebuilds the bitmap from the tags (k_occ_from_tags),
             // one streaming pass instead of a memory-side atomic per claim
-            const uint32_t gs = find_or_insert<KW, false, NA>(a, k[u], h[u], gidx, first_ins, d[u], v[u], claimed);
+            const uint32_t gs = find_or_insert<KW, false, NA, WIDE>(a, k[u], h[u], gidx, first_ins, d[u], v[u], claimed);
             if (gs == SLOT_OVF || claimed) continue;
 #pragma unroll
             for (int x = 0; x < NA; ++x)
@@ -2126,6 +2200,7 @@ struct igx_table {
     uint32_t naggs = 0;
     uint64_t cap = 0;            // distinct keys promised by the caller
     uint64_t nslots = 0;
+    bool wide = false;           // S x KR >= 4 GiB (or IGX_GB_WIDE=1): 64-bit record addressing, no cached form
     uint32_t sbits = 0;          // log2 nslots
     uint32_t rbits = 0;          // log2 probe-region slots (probing wraps inside a region)
     uint8_t *krec = nullptr;
@@ -2283,12 +2358,10 @@ extern "C" int igx_groupby_create(igx_ctx *ctx, const uint32_t *key_widths, uint
     // probe regions of max(1024, S / 16384) slots: up to 16K regions, so a bucket of the
     // partitioned form can own whole regions
     t->rbits = std::max<uint32_t>(10, t->sbits > 14 ? t->sbits - 14 : 0);
-    if (ns * t->krec_len >= (1ull << 32)) {
-        const uint32_t r = t->krec_len;
-        delete t;
-        return igx_fail(ctx, IGX_ENOTSUP, "groupby_create: table of %llu x %u B exceeds 4 GiB",
-                        (unsigned long long)ns, r);
-    }
+    // key records past a buffer descriptor's 4 GiB: the wide instances (per-lane 64-bit addresses)
+    t->wide = ns * t->krec_len >= (1ull << 32);
+    if (const char *d = std::getenv("IGX_GB_WIDE"))   // A/B and test knob: wide instances on a narrow-sized table
+        t->wide = t->wide || std::strtoul(d, nullptr, 0) != 0;
     const uint64_t tiles = (ns + CT - 1) / CT;
     hipError_t e = hipMalloc(&t->krec, ns * t->krec_len);
     if (e == hipSuccess) e = hipMemsetAsync(t->krec, 0, ns * t->krec_len, ctx->stream);
@@ -2315,7 +2388,7 @@ extern "C" int igx_groupby_create(igx_ctx *ctx, const uint32_t *key_widths, uint
     // tuning / A-B knob (tools/gpu/ab_modes.sh): the initial mode, as igx_groupby_set_mode
     if (const char *m = std::getenv("IGX_GB_MODE")) {
         const unsigned long v = std::strtoul(m, nullptr, 0);
-        if (v <= IGX_GB_PART) t->mode = (uint32_t)v;
+        if (v <= IGX_GB_PART && !(t->wide && v == IGX_GB_CACHED)) t->mode = (uint32_t)v;   // no cached form on a wide table
     }
     if (const char *m = std::getenv("IGX_GB_PERSIST")) t->persist = std::strtoul(m, nullptr, 0) != 0;   // A/B knob
     if (const char *m = std::getenv("IGX_GB_SEED")) t->seed_on = std::strtoul(m, nullptr, 0) != 0;       // A/B knob
@@ -2362,7 +2435,7 @@ extern "C" int igx_groupby_reset(igx_table *t) {
     rg.ng = t->n_groups;
     rg.vrec = t->vrec;
     rg.vw = t->vrec_len / 8;
-    const bool planned_cached = !(t->mode == IGX_GB_DIRECT || t->mode == IGX_GB_PART ||
+    const bool planned_cached = !(t->wide || t->mode == IGX_GB_DIRECT || t->mode == IGX_GB_PART ||
                                   (t->mode == IGX_GB_AUTO && t->direct_left > 0));
     rg.may = t->persist && !wrapped && t->fin_since_update && rg.limit > 0 && planned_cached ? 1u : 0u;
     t->gen_planned = rg.may != 0;
@@ -2488,25 +2561,25 @@ static void launch_gb(igx_ctx *ctx, GbArgs &a, uint32_t blocks) {
 // The grid is exactly the blocks that are resident at once (the occupancy the kernel's
 // registers allow): every block sweeps a fixed share of the rows, so a block that had to wait
 // for a free slot would run its whole share after the others -- a tail of up to 1/8 of the time.
-template <class L, int NA>
+template <class L, int NA, bool WIDE = false>
 static void launch_direct_as(igx_ctx *ctx, GbArgs &a) {
     static int per_cu = 0;
     if (!per_cu) {
         int b = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, reinterpret_cast<const void *>(k_groupby_direct<L, NA>),
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, reinterpret_cast<const void *>(k_groupby_direct<L, NA, WIDE>),
                                                          256, 0) != hipSuccess || b < 1)
             b = 4;
         per_cu = std::min(b, 8);
     }
     const uint64_t want = (a.n + 255) / 256;
     const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)ctx->num_cus * per_cu));
-    hipLaunchKernelGGL((k_groupby_direct<L, NA>), dim3(blocks), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL((k_groupby_direct<L, NA, WIDE>), dim3(blocks), dim3(256), 0, ctx->stream, a);
 }
 
-template <class L>
+template <class L, bool WIDE = false>
 static void launch_direct(igx_ctx *ctx, GbArgs &a) {
-    if (a.naggs <= 2) launch_direct_as<L, 2>(ctx, a);
-    else launch_direct_as<L, AMAX>(ctx, a);
+    if (a.naggs <= 2) launch_direct_as<L, 2, WIDE>(ctx, a);
+    else launch_direct_as<L, AMAX, WIDE>(ctx, a);
 }
 
 static int grow(igx_ctx *ctx, void **p, size_t *have, size_t need) {
@@ -2523,7 +2596,7 @@ static int grow(igx_ctx *ctx, void **p, size_t *have, size_t need) {
 // The partitioned form (k_groupby_part.h): passes K, O, S, A, B, C -- or, in the region
 // variant (AUTO's miss-heavy intervals), A, T, B, I, C: no count pass, buckets filled through
 // cursors into regions of 1.25x their share of the rows.
-template <class L, int NV>
+template <class L, int NV, bool WIDE = false>
 static int launch_part_as(igx_table *t, igx_ctx *ctx, GbArgs &a, PartArgs &p, bool region) {
     constexpr int KW = L::KW;
     constexpr uint32_t TRA = PTA * part_rows<KW, NV>();
@@ -2640,11 +2713,11 @@ static int launch_part_as(igx_table *t, igx_ctx *ctx, GbArgs &a, PartArgs &p, bo
     constexpr bool PEK = pack_words<L>() <= 3;   // a packed-entry pass C exists for this layout
     static size_t lds_set[6] = {0, 0, 0, 0, 0, 0};
     const void *kern[6] = {reinterpret_cast<const void *>(k_gbp_count<L, NV>),
-                           reinterpret_cast<const void *>(k_gbp_a<L, NV>),
-                           reinterpret_cast<const void *>(k_gbp_b<L, NV>),
-                           reinterpret_cast<const void *>(k_gbp_c<L, NV, AMAX>),
-                           reinterpret_cast<const void *>(k_gbp_c<L, NV, 0>),
-                           reinterpret_cast<const void *>(k_gbp_c<L, NV, 0, PEK>)};
+                           reinterpret_cast<const void *>(k_gbp_a<L, NV, WIDE>),
+                           reinterpret_cast<const void *>(k_gbp_b<L, NV, WIDE>),
+                           reinterpret_cast<const void *>(k_gbp_c<L, NV, AMAX, false, WIDE>),
+                           reinterpret_cast<const void *>(k_gbp_c<L, NV, 0, false, WIDE>),
+                           reinterpret_cast<const void *>(k_gbp_c<L, NV, 0, PEK, WIDE>)};
     const bool pe_c = PEK && p.pe;
     const size_t need[6] = {lds_k, lds_a, lds_b, t->naggs ? lds_c : 0, t->naggs || pe_c ? 0 : lds_c, pe_c ? lds_c : 0};
     for (int i = 0; i < 6; ++i) {
@@ -2656,10 +2729,10 @@ static int launch_part_as(igx_table *t, igx_ctx *ctx, GbArgs &a, PartArgs &p, bo
     const uint32_t cus = (uint32_t)ctx->num_cus;
     if (region) {
         IGX_HIP(ctx, hipMemsetAsync(p.rc1, 0, 4ull * (U1 * RC1_PAD + NB * p.c2pad), ctx->stream));
-        hipLaunchKernelGGL((k_gbp_a<L, NV>), dim3(p.tiles_a), dim3(PTA), lds_a, ctx->stream, a, p);
+        hipLaunchKernelGGL((k_gbp_a<L, NV, WIDE>), dim3(p.tiles_a), dim3(PTA), lds_a, ctx->stream, a, p);
         if (p.dbg & 256u) return IGX_OK;   // diagnostics: stop after pass A (the table is left unset)
         hipLaunchKernelGGL(k_gbr_tiles, dim3(1), dim3(1024), 0, ctx->stream, p);
-        hipLaunchKernelGGL((k_gbp_b<L, NV>), dim3((unsigned)tiles_b), dim3(PTA), lds_b, ctx->stream, a, p);
+        hipLaunchKernelGGL((k_gbp_b<L, NV, WIDE>), dim3((unsigned)tiles_b), dim3(PTA), lds_b, ctx->stream, a, p);
         if (p.dbg & 512u) return IGX_OK;   // ... after pass B
         hipLaunchKernelGGL(k_gbr_items, dim3(1), dim3(1024), 0, ctx->stream, p);
     }
@@ -2671,17 +2744,17 @@ static int launch_part_as(igx_table *t, igx_ctx *ctx, GbArgs &a, PartArgs &p, bo
     hipLaunchKernelGGL(k_gbp_scan, dim3(1), dim3(1024), 0, ctx->stream, p);
     hipLaunchKernelGGL(k_gbp_offs, dim3(p.nchunk), dim3(PTA), 0, ctx->stream, p);
     if (p.dbg & 1024u) return IGX_OK;   // diagnostics: stop after the count and the scans
-    hipLaunchKernelGGL((k_gbp_a<L, NV>), dim3(p.tiles_a), dim3(PTA), lds_a, ctx->stream, a, p);
+    hipLaunchKernelGGL((k_gbp_a<L, NV, WIDE>), dim3(p.tiles_a), dim3(PTA), lds_a, ctx->stream, a, p);
     if (p.dbg & 256u) return IGX_OK;   // diagnostics: stop after pass A (the table is left unset)
-    hipLaunchKernelGGL((k_gbp_b<L, NV>), dim3((unsigned)tiles_b), dim3(PTA), lds_b, ctx->stream, a, p);
+    hipLaunchKernelGGL((k_gbp_b<L, NV, WIDE>), dim3((unsigned)tiles_b), dim3(PTA), lds_b, ctx->stream, a, p);
     if (p.dbg & 512u) return IGX_OK;   // ... after pass B
     }
     if (t->naggs)
-        hipLaunchKernelGGL((k_gbp_c<L, NV, AMAX>), dim3(2 * cus), dim3(PTC), lds_c, ctx->stream, a, p);
+        hipLaunchKernelGGL((k_gbp_c<L, NV, AMAX, false, WIDE>), dim3(2 * cus), dim3(PTC), lds_c, ctx->stream, a, p);
     else if (pe_c)   // distinct-only with packed entries (C4)
-        hipLaunchKernelGGL((k_gbp_c<L, NV, 0, PEK>), dim3(2 * cus), dim3(PTC), lds_c, ctx->stream, a, p);
+        hipLaunchKernelGGL((k_gbp_c<L, NV, 0, PEK, WIDE>), dim3(2 * cus), dim3(PTC), lds_c, ctx->stream, a, p);
     else   // distinct-only: no aggregate decode or accumulate in the per-record path
-        hipLaunchKernelGGL((k_gbp_c<L, NV, 0>), dim3(2 * cus), dim3(PTC), lds_c, ctx->stream, a, p);
+        hipLaunchKernelGGL((k_gbp_c<L, NV, 0, false, WIDE>), dim3(2 * cus), dim3(PTC), lds_c, ctx->stream, a, p);
     return IGX_OK;
 }
 
@@ -2771,6 +2844,11 @@ static int launch_part(igx_table *t, igx_ctx *ctx, GbArgs &a) {
     const bool region = (t->mode == IGX_GB_AUTO || std::getenv("IGX_GBP_REGION")) && !std::getenv("IGX_GBP_EXACT") &&
                         t->region_off == 0;
     t->interval_region = t->interval_region || region;
+    if (t->wide) {
+        if (nv == 0) return launch_part_as<L, 0, true>(t, ctx, a, p, region);
+        if (nv <= 2) return launch_part_as<L, 2, true>(t, ctx, a, p, region);
+        return launch_part_as<L, PNV, true>(t, ctx, a, p, region);
+    }
     if (nv == 0) return launch_part_as<L, 0>(t, ctx, a, p, region);
     if (nv <= 2) return launch_part_as<L, 2>(t, ctx, a, p, region);
     return launch_part_as<L, PNV>(t, ctx, a, p, region);
@@ -2796,7 +2874,7 @@ static void bind_records(const igx_table *t, GbArgs &a) {
     a.krec = t->krec;
     a.vrec = t->vrec;
     a.krec_len = t->krec_len;
-    a.krec_total = (uint32_t)(t->nslots * t->krec_len);
+    a.krec_total = t->wide ? 0u : (uint32_t)(t->nslots * t->krec_len);
     a.vrec_words = t->vrec_len / 8;
     a.vrec_total = t->nslots * t->vrec_len < (1ull << 32) ? (uint32_t)(t->nslots * t->vrec_len) : 0u;
     a.err = t->err;
@@ -2829,6 +2907,10 @@ static int seeds_compute_static(igx_table *t, igx_ctx *ctx, const GbArgs &a) {
         igx_table *st = nullptr;
         int rc = igx_groupby_create(ctx, t->key_widths, t->nkeys, &cnt, 1, std::max<uint64_t>(S, 4ull * E), &st);
         if (rc) return rc;
+        if (st->wide) {   // the sample runs the cached form, which a wide table does not have
+            igx_groupby_destroy(st);
+            return IGX_ENOTSUP;
+        }
         st->persist = false;
         st->seed_on = false;
         st->mode = IGX_GB_CACHED;
@@ -2911,6 +2993,13 @@ static int launch_form(igx_table *t, igx_ctx *ctx, GbArgs &a, uint32_t blocks) {
         // update runs cached instead (the forms share the table protocol, so they may mix
         // within an interval), and AUTO measures again at the next interval
         (void)hipGetLastError();
+        if (t->wide) {   // no cached form: the rest of the interval runs direct (finalize then also
+            t->interval_part = false;   // reads the occupancy off the tags, OR-ed into the claimers' bits)
+            t->interval_direct = true;
+            a = saved;
+            launch_direct<L, true>(ctx, a);
+            return IGX_OK;
+        }
         if (t->interval_probe)   // the cached kernel measures this interval itself: drop the estimate
             IGX_HIP(ctx, hipMemsetAsync(t->err + 2, 0, 8, ctx->stream));
         t->interval_part = false;
@@ -2919,8 +3008,10 @@ static int launch_form(igx_table *t, igx_ctx *ctx, GbArgs &a, uint32_t blocks) {
         a = saved;
     }
     if (t->interval_direct) {
-        launch_direct<L>(ctx, a);
+        if (t->wide) launch_direct<L, true>(ctx, a);
+        else launch_direct<L>(ctx, a);
     } else {
+        if (t->wide) return igx_fail(ctx, IGX_ENOTSUP, "groupby_update: no cached form on a wide table");
         t->occb_dirty = true;   // the cached form's claims mark the byte map
         if (t->rows_fed == a.n) {   // the interval's first update decides whether it is seeded
             uint64_t min_rows = SEED_MIN_ROWS;
@@ -2951,6 +3042,10 @@ static int launch_form(igx_table *t, igx_ctx *ctx, GbArgs &a, uint32_t blocks) {
 extern "C" int igx_groupby_set_mode(igx_table *t, uint32_t mode) {
     if (!t) return IGX_EINVAL;
     if (mode > IGX_GB_PART) return igx_fail(t->ctx, IGX_EINVAL, "groupby_set_mode: mode %u", mode);
+    if (t->wide && mode == IGX_GB_CACHED)
+        return igx_fail(t->ctx, IGX_ENOTSUP, "groupby_set_mode: the cached form is not available on a wide table "
+                                             "(%llu slots x %u B of key records; 64-bit record addressing)",
+                        (unsigned long long)t->nslots, t->krec_len);
     t->mode = mode;
     t->direct_left = 0;
     return IGX_OK;
@@ -3226,14 +3321,16 @@ static int choose_form(igx_table *t, const GbArgs &a) {
     igx_ctx *ctx = t->ctx;
     if (t->rows_fed == a.n) {
         t->interval_direct = t->mode == IGX_GB_DIRECT;
-        t->interval_part = t->mode == IGX_GB_PART || (t->mode == IGX_GB_AUTO && t->direct_left > 0);
+        // a wide table has no cached form: AUTO plans every interval partitioned (no run to
+        // count down, no re-probe of the stream)
+        t->interval_part = t->mode == IGX_GB_PART || (t->mode == IGX_GB_AUTO && (t->wide || t->direct_left > 0));
         t->interval_probe = false;
         t->probe_rows = 0;
-        if (t->mode == IGX_GB_AUTO && t->direct_left > 0) t->interval_probe = --t->direct_left == 0;
+        if (t->mode == IGX_GB_AUTO && !t->wide && t->direct_left > 0) t->interval_probe = --t->direct_left == 0;
         t->interval_region = false;
         if (t->region_off > 0) --t->region_off;
     }
-    if (std::getenv("IGX_GB_DEBUG")) t->interval_direct = t->interval_part = false;   // diagnostics: cached form
+    if (std::getenv("IGX_GB_DEBUG") && !t->wide) t->interval_direct = t->interval_part = false;   // diagnostics: cached form
     if (t->gen_planned && (t->interval_direct || t->interval_part)) {
         hipLaunchKernelGGL(k_gen_restart, dim3(1), dim3(1), 0, ctx->stream, a.gen, t->ep);
         IGX_HIP(ctx, hipGetLastError());

@@ -448,7 +448,7 @@ __global__ __launch_bounds__(PTA) void k_gbp_offs(PartArgs p) {
     scan_column(p.cnt1 + (uint64_t)t0 * F1 + threadIdx.x, F1, t1 - t0, p.csum[(uint64_t)c * F1 + threadIdx.x]);
 }
 
-template <int KW, int NA>
+template <int KW, int NA, bool WIDE = false>
 __device__ __forceinline__ void hbm_merge(const GbArgs &a, const uint32_t (&k)[KW], uint64_t h,
                                           const uint64_t (&v)[NA], uint64_t first);
 
@@ -473,7 +473,7 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long x)
 // are mostly that key's: they are pre-combined across the wave first (wave64 ballot +
 // shuffle: every distinct key's sums and minimum first index reduced onto its lowest lane),
 // and only the leaders merge -- one record's atomics per key per wave instead of per row.
-template <class L>
+template <class L, bool WIDE = false>
 __device__ __forceinline__ void region_spill(const GbArgs &a, const PartArgs &p, bool spill, const uint32_t *rec) {
     constexpr int KW = L::KW;
     const uint64_t any = __ballot(spill);
@@ -512,7 +512,7 @@ __device__ __forceinline__ void region_spill(const GbArgs &a, const PartArgs &p,
         if ((int)lane == ld) gidx = f;
         else if (same) lead = false;
     }
-    if (lead) hbm_merge<KW, AMAX>(a, k, h, v, gidx);
+    if (lead) hbm_merge<KW, AMAX, WIDE>(a, k, h, v, gidx);
 }
 
 // a partition pass's record store, written once and read back only by the next pass.  Pass
@@ -530,7 +530,7 @@ __device__ __forceinline__ void st_rec(uint4 *p, const uint4 q) {
 // The tile's rows stay in registers (R per thread, all loads issued at once); a row's rank
 // in its bucket comes from an LDS atomic, so the records are staged in LDS already sorted
 // and leave as whole runs, 16 B per lane.
-template <class L, int NV>
+template <class L, int NV, bool WIDE = false>
 __global__ __launch_bounds__(PTA) void k_gbp_a(GbArgs a, PartArgs p) {
     constexpr int KW = L::KW;
     constexpr int R = part_rows<KW, NV>();
@@ -597,7 +597,7 @@ __global__ __launch_bounds__(PTA) void k_gbp_a(GbArgs a, PartArgs p) {
         } else if (!p.reg1) st_rec<false>(&out[(uint64_t)g * rq + q], stage[qi]);
         else if (g < p.reg1) st_rec<false>(&out[((uint64_t)((b << p.s1log) + sl) * p.reg1 + g) * rq + q], stage[qi]);
         else spill = q == 0;
-        if (p.reg1) region_spill<L>(a, p, spill, reinterpret_cast<const uint32_t *>(stage + (uint64_t)(live ? j : 0u) * rq));
+        if (p.reg1) region_spill<L, WIDE>(a, p, spill, reinterpret_cast<const uint32_t *>(stage + (uint64_t)(live ? j : 0u) * rq));
     }
 }
 
@@ -665,7 +665,7 @@ __host__ __device__ inline bool gbp_b_regs(const PartArgs &p) {
     return p.rq == 1 && p.trb <= 16 * PTA && !(p.dbg & 6u);
 }
 
-template <class L, int RQ, int MB>   // MB records per thread (trb <= MB PTA)
+template <class L, int RQ, int MB, bool WIDE = false>   // MB records per thread (trb <= MB PTA)
 __device__ __forceinline__ void gbp_b_run(const GbArgs &a, const PartArgs &p, uint8_t *lds_raw, const u4v *src,
                                           uint32_t cnt, uint32_t b1) {
     constexpr int KW = L::KW;
@@ -734,14 +734,14 @@ __device__ __forceinline__ void gbp_b_run(const GbArgs &a, const PartArgs &p, ui
         } else if (!p.reg2) st_rec<true>(&out[(uint64_t)g * RQ + q], stage[qi]);
         else if (g < p.reg2) st_rec<true>(&out[((uint64_t)((b1 << p.f2) + b) * p.reg2 + g) * RQ + q], stage[qi]);
         else spill = q == 0;
-        if (p.reg2) region_spill<L>(a, p, spill, reinterpret_cast<const uint32_t *>(stage + (uint64_t)(live ? jj : 0u) * RQ));
+        if (p.reg2) region_spill<L, WIDE>(a, p, spill, reinterpret_cast<const uint32_t *>(stage + (uint64_t)(live ? jj : 0u) * RQ));
     }
 }
 
 // B tile `blockIdx.x` = records [j * trb, (j + 1) * trb) of first-level bucket b1 in recs1
 // (contiguous): loaded flat into LDS (coalesced), ranked by the next f2 hash bits with LDS
 // atomics, and each final bucket's run written at a cursor reserved with one atomic.
-template <class L, int NV>
+template <class L, int NV, bool WIDE = false>
 __global__ __launch_bounds__(PTA) void k_gbp_b(GbArgs a, PartArgs p) {
     constexpr int KW = L::KW;
     constexpr int U = 16;              // quads in flight per thread: a whole tile at once
@@ -764,7 +764,7 @@ __global__ __launch_bounds__(PTA) void k_gbp_b(GbArgs a, PartArgs p) {
     const u4v *src = reinterpret_cast<const u4v *>(p.recs1) + (uint64_t)s * rq;
     if constexpr (PackKey<L>::known && L::KW <= 8) {   // (wider keys never have 1-2 quad records)
         if (gbp_b_regs(p)) {
-            gbp_b_run<L, 1, 16>(a, p, lds_raw, src, cnt, b1);
+            gbp_b_run<L, 1, 16, WIDE>(a, p, lds_raw, src, cnt, b1);
             return;
         }
     }
@@ -813,7 +813,7 @@ __global__ __launch_bounds__(PTA) void k_gbp_b(GbArgs a, PartArgs p) {
         } else if (!p.reg2) st_rec<true>(&out[(uint64_t)g * rq + q], stage[sidx * rq + q]);
         else if (g < p.reg2) st_rec<true>(&out[((uint64_t)((b1 << p.f2) + b) * p.reg2 + g) * rq + q], stage[sidx * rq + q]);
         else spill = q == 0;
-        if (p.reg2) region_spill<L>(a, p, spill, reinterpret_cast<const uint32_t *>(stage + (uint64_t)sidx * rq));
+        if (p.reg2) region_spill<L, WIDE>(a, p, spill, reinterpret_cast<const uint32_t *>(stage + (uint64_t)sidx * rq));
     }
 }
 
@@ -912,14 +912,16 @@ __device__ __forceinline__ int at_find_insert(const AggTab<KW> &T, const uint32_
 }
 
 // one row (or one LDS group) merged into the HBM table with CAS claims and atomics
-template <int KW, int NA>
+// (WIDE: the table's record addressing, k_groupby.hip probe_issue)
+template <int KW, int NA, bool WIDE>
 __device__ __forceinline__ void hbm_merge(const GbArgs &a, const uint32_t (&k)[KW], uint64_t h,
                                           const uint64_t (&v)[NA], uint64_t first) {
-    uint32_t d[probe_quads<KW>() * 4];
-    probe_issue<KW>(a, h, d);
+    probe_regs<KW, WIDE> d;
+    probe_issue<KW, WIDE>(a, h, d);
+    probe_wait<KW, WIDE>(d);
     uint64_t first_ins = 0;
     bool claimed = false;
-    const uint32_t gs = find_or_insert<KW, true, NA>(a, k, h, first, first_ins, d, v, claimed);
+    const uint32_t gs = find_or_insert<KW, true, NA, WIDE>(a, k, h, first, first_ins, d, v, claimed);
     if (gs == SLOT_OVF || claimed) return;   // a claim wrote the values into the new record
 #pragma unroll
     for (int x = 0; x < NA; ++x)
@@ -1030,7 +1032,7 @@ __device__ __forceinline__ uint64_t lds_hash(const uint32_t (&k)[KW]) {
     return x;
 }
 
-template <class L, int NA>
+template <class L, int NA, bool WIDE = false>
 __device__ __forceinline__ void c_row(const GbArgs &a, const PartArgs &p, const AggTab<L::KW> &T, bool ok,
                                       const uint32_t *rec) {
     constexpr int KW = L::KW;
@@ -1052,7 +1054,7 @@ __device__ __forceinline__ void c_row(const GbArgs &a, const PartArgs &p, const 
         if (gidx < T.first[ei]) atomicMin(reinterpret_cast<unsigned long long *>(&T.first[ei]), (unsigned long long)gidx);
     } else {
         T.flag[0] = 1;
-        hbm_merge<KW, nax(NA)>(a, k, hash_key<KW>(k), v, gidx);
+        hbm_merge<KW, nax(NA), WIDE>(a, k, hash_key<KW>(k), v, gidx);
     }
 }
 
@@ -1109,7 +1111,7 @@ __device__ __forceinline__ int pe_find_insert(uint8_t *tg8, uint4 *ent, uint32_t
     }
 }
 
-template <class L>
+template <class L, bool WIDE = false>
 __device__ __forceinline__ void c_row_pe(const GbArgs &a, const PartArgs &p, uint8_t *tg8, uint4 *ent, uint32_t E,
                                          uint32_t *flag, bool ok, const uint32_t *rec) {
     constexpr int PW = (int)pack_words<L>();
@@ -1129,7 +1131,7 @@ __device__ __forceinline__ void c_row_pe(const GbArgs &a, const PartArgs &p, uin
         uint32_t k[KW];
         lds_key<L>(p, rec, k);
         const uint64_t v[1] = {0};
-        hbm_merge<KW, 1>(a, k, hash_key<KW>(k), v, a.base_idx + idx);
+        hbm_merge<KW, 1, WIDE>(a, k, hash_key<KW>(k), v, a.base_idx + idx);
     }
 }
 
@@ -1138,7 +1140,7 @@ __device__ __forceinline__ void c_row_pe(const GbArgs &a, const PartArgs &p, uin
 // over the whole kernel: the two paths together spilled 100-300 SGPRs into VGPR lanes).
 // Two 80 KB blocks of PTC threads per CU (one 1 024-thread block over the whole 160 KB, half
 // the buckets, measured slower: DESIGN.md §4 "Round 6: pass C").
-template <class L, int NV, int NA, bool PE = false>
+template <class L, int NV, int NA, bool PE = false, bool WIDE = false>
 __global__ __launch_bounds__(PTC) void k_gbp_c(GbArgs a, PartArgs p) {
     constexpr uint32_t TPB = PTC;
     constexpr int KW = L::KW;
@@ -1210,8 +1212,8 @@ __global__ __launch_bounds__(PTC) void k_gbp_c(GbArgs a, PartArgs p) {
             for (uint32_t u = 0; u < uc; ++u) {
                 const uint32_t i = u * TPB + threadIdx.x;
                 const uint32_t *rec = reinterpret_cast<const uint32_t *>(stage + (uint64_t)min(i, RC - 1) * rq);
-                if constexpr (PE) c_row_pe<L>(a, p, tg8, ent, E, T.flag, r0 + i < e, rec);
-                else c_row<L, NA>(a, p, T, r0 + i < e, rec);
+                if constexpr (PE) c_row_pe<L, WIDE>(a, p, tg8, ent, E, T.flag, r0 + i < e, rec);
+                else c_row<L, NA, WIDE>(a, p, T, r0 + i < e, rec);
             }
         }
         __syncthreads();
@@ -1258,7 +1260,7 @@ __global__ __launch_bounds__(PTC) void k_gbp_c(GbArgs a, PartArgs p) {
                 const uint64_t v[1] = {0};
                 const uint64_t h = hash_key<KW>(k), f = a.base_idx + q.w;
                 if (owned) flush_owned<KW, 1>(a, T, k, h, v, f, sb, p.sb_log);
-                else hbm_merge<KW, 1>(a, k, h, v, f);
+                else hbm_merge<KW, 1, WIDE>(a, k, h, v, f);
                 continue;
             }
             uint32_t k[KW];
@@ -1270,7 +1272,7 @@ __global__ __launch_bounds__(PTC) void k_gbp_c(GbArgs a, PartArgs p) {
             for (int q = 0; q < NA; ++q) v[q] = q < (int)a.naggs ? T.agg[(uint64_t)q * E + x] : 0ull;
             const uint64_t h = hash_key<KW>(k);
             if (owned) flush_owned<KW, nax(NA)>(a, T, k, h, v, T.first[x], sb, p.sb_log);
-            else hbm_merge<KW, nax(NA)>(a, k, h, v, T.first[x]);
+            else hbm_merge<KW, nax(NA), WIDE>(a, k, h, v, T.first[x]);
         }
         __syncthreads();
         if (owned) {

@@ -311,7 +311,8 @@ def unpack_rows(rows, key_widths, naggs):
 
 def owner_table(key_widths, out_widths, capacity):
     """The owner's merge table: SUM of the partials per aggregate, first = MIN, in the cached
-    form.  A merge's rows are nearly all LDS misses (each key arrives once per rank that saw it),
+    form (a wide table, capacity past the 4 GiB of key records a cached table addresses: AUTO's
+    partitioned form).  A merge's rows are nearly all LDS misses (each key arrives once per rank that saw it),
     which would send AUTO to the partitioned form; but the cached form keeps the owner's keys
     across intervals and finds them, and measures faster (profiles/r06/emulated_rank8_*.json,
     rank 0 of 8: C4 0.98 -> 0.62 ms, C5 1.67 -> 1.53 ms)."""
@@ -319,8 +320,19 @@ def owner_table(key_widths, out_widths, capacity):
     nk = len(key_widths)
     spec = [_abi.Agg(_abi.AGG_SUM, nk + x, _abi.NO_COL, ow, 0) for x, ow in enumerate(out_widths)]
     t = engine.Table(key_widths, spec, max(1, capacity))
-    t.set_mode(_abi.GB_CACHED)
+    _prefer_cached(t)
     return t
+
+
+def _prefer_cached(table):
+    """The cached form where the table has one.  A wide table (key records of 4 GiB or more, see
+    igx_groupby_create) does not: it stays in AUTO, which runs every interval partitioned."""
+    from . import _abi
+    try:
+        table.set_mode(_abi.GB_CACHED)
+    except _abi.IgxError as e:
+        if e.code != _abi.IGX_ENOTSUP:
+            raise
 
 
 def merge_partials(rows, key_widths, out_widths, capacity, table=None, sync=True):
@@ -335,7 +347,7 @@ def merge_partials(rows, key_widths, out_widths, capacity, table=None, sync=True
     if table is None:
         spec = [_abi.Agg(_abi.AGG_SUM, nk + x, _abi.NO_COL, ow, 0) for x, ow in enumerate(out_widths)]
         table = engine.Table(key_widths, spec, max(1, capacity))
-        table.set_mode(_abi.GB_CACHED)   # see owner_table()
+        _prefer_cached(table)   # see owner_table()
     else:
         table.reset()
     n = rows.shape[0]

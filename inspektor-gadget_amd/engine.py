@@ -213,7 +213,11 @@ sort_perm_kinds = sort_perm
 # group-by table
 # ------------------------------------------------------------------------------------
 class Table:
-    """igx_table: keyed aggregation with first-occurrence tracking."""
+    """igx_table: keyed aggregation with first-occurrence tracking.
+
+    capacity (at most 2^28) bounds the interval's distinct keys.  A table whose key records
+    reach 4 GiB (slots x key stride, e.g. more than 8.39M groups of top tcp's key) is *wide*:
+    it runs the direct and partitioned forms only (see igx_groupby_create in include/igx.h)."""
 
     def __init__(self, key_widths, aggs, capacity, ctx=None):
         self.ctx = context() if ctx is None else ctx
@@ -260,7 +264,9 @@ class Table:
         self.ctx.check(self.ctx.L.igx_groupby_reset(self.h))
 
     def set_mode(self, mode):
-        """igx_groupby_set_mode: _abi.GB_AUTO (default), GB_CACHED, GB_DIRECT or GB_PART."""
+        """igx_groupby_set_mode: _abi.GB_AUTO (default), GB_CACHED, GB_DIRECT or GB_PART.
+        GB_CACHED on a wide table raises IgxError (code IGX_ENOTSUP) with the library's message;
+        the table keeps its mode."""
         self.ctx.check(self.ctx.L.igx_groupby_set_mode(self.h, mode))
 
     def finalize(self, sync=True):
