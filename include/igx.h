@@ -497,6 +497,47 @@ int igx_hist_log2(igx_ctx *ctx, const uint32_t *dev, const uint32_t *cont,
 int igx_log2_slots(igx_ctx *ctx, const int64_t *delta, uint64_t nrows, uint64_t divisor, uint32_t nslots,
                    uint8_t *slot, uint8_t *keep);
 
+/* ---- block-I/O request pairing ----------------------------------------------------------- */
+/* The start / issue / done join that top block-io and profile block-io run through hash maps
+ * keyed by `struct request *`: biotop.bpf.c:41-130 (blk_account_io_start stores who_t in
+ * whobyreq, blk_mq_start_request stores start_req_t{ts, data_len} in start, blk_account_io_done
+ * looks both up, forms delta_us and deletes both) and biolatency.bpf.c:47-154 (block_rq_insert /
+ * block_rq_issue store ts, block_rq_complete looks it up, forms the latency and deletes it).
+ *
+ * A batch is nrows probe rows in stream order (row i before row i + 1): req (u64, the request
+ * pointer), kind (u8, enum igx_req_kind), ts (u64, ktime ns); rows with valid[i] == 0 (valid
+ * nullable) or any other kind do not exist for the join (the filters a probe applies before it
+ * touches the maps).  Every req starts the batch with neither entry.  Per req, in row order:
+ *   IGX_REQ_START  who := this row (overwrites)
+ *   IGX_REQ_ISSUE  issue := this row (overwrites)
+ *   IGX_REQ_DONE   without an issue entry: nothing, and who is kept (biotop.bpf.c:97-99);
+ *                  else emit (this row, the issue row, the who row or IGX_NO_COL,
+ *                  delta = ts[this] - ts[issue] mod 2^64) and delete both entries
+ * done_row, issue_row, who_row, delta (device, nrows entries each): entry j describes the j-th
+ * emitting DONE in stream order; igx_take of a who_row of IGX_NO_COL yields a zero row, the
+ * reference's zero-initialised info_t.  *d_ndone (device u64) is their number.  The START and
+ * ISSUE rows whose entries are still there at the end of the batch go to pend_row in stream
+ * order: nothing is written past pend_cap entries, and *d_npend (device u64) is their true
+ * number, which may exceed pend_cap (as igx_groupby_select_ge's count).  State crosses a batch
+ * boundary in band: put those rows, every column, in that order, in front of the next batch.
+ * The maps' max_entries is not reproduced.  biolatency's negative delta (:115-117) is an
+ * emitting DONE like any other; igx_log2_slots' keep drops it.
+ *
+ * nrows <= 2^32 - 2 (IGX_EINVAL otherwise, checked before anything else is looked at); 0 is
+ * valid.  req, ts, delta and the counts are 8-byte aligned, the row outputs 4-byte aligned
+ * (IGX_EINVAL otherwise).  The outputs may not overlap the inputs or each other.  Work per row
+ * does not depend on how long a req's run is; scratch of about 10 bytes per row beside the
+ * sort's (IGX_ENOMEM if it cannot be had).  One host synchronisation (the sort's digit plan);
+ * the counts stay on the device.  igx_req_join_tile: the rows per tile of the device scan
+ * (sizes around it are where tiles hand state over). */
+enum igx_req_kind { IGX_REQ_START = 0, IGX_REQ_ISSUE = 1, IGX_REQ_DONE = 2 };
+int igx_req_join(igx_ctx *ctx, const uint64_t *req, const uint8_t *kind, const uint64_t *ts,
+                 const uint8_t *valid /*nullable*/, uint64_t nrows,
+                 uint32_t *done_row, uint32_t *issue_row, uint32_t *who_row, uint64_t *delta,
+                 uint64_t *d_ndone,
+                 uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend);
+int igx_req_join_tile(void);
+
 /* ---- group:sum of float columns, IP text --------------------------------------------- */
 /* GroupEntries' float group:sum (group.go:133-156, flattenValues): perm (device u32, n) is a
  * stable sort of the rows by the group key (key_bytes at row * key_stride of keys); each run

@@ -30,6 +30,7 @@ MAX_REF = 256
 AGG_COUNT, AGG_SUM = 0, 1
 FILTER_ANY, FILTER_NIL_MATCH = 1, 2
 GB_AUTO, GB_CACHED, GB_DIRECT, GB_PART = 0, 1, 2, 3
+REQ_START, REQ_ISSUE, REQ_DONE = 0, 1, 2
 
 
 class SchemaCol(C.Structure):
@@ -160,6 +161,8 @@ SIGNATURES = [
     ("igx_hist_log2", _I, [_VP, _VP, _VP, _VP, _U64, C.POINTER(_U32), _U32, _U32, _U64, _U32,
                            _VP]),
     ("igx_log2_slots", _I, [_VP, _VP, _U64, _U64, _U32, _VP, _VP]),
+    ("igx_req_join", _I, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _VP, _VP, _VP, _U64, _VP]),
+    ("igx_req_join_tile", _I, []),
     ("igx_partition_rows", _I, [_VP, _VP, _U64, _U32, _U32, _U32, _VP, _VP]),
     ("igx_partition_groups", _I, [_VP, _VP, _VP, _U32, _VP, _U64, _VP]),
     ("igx_dist_get_unique_id", _I, [_VP]),

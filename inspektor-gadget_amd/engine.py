@@ -502,6 +502,51 @@ def hist_log2_keyed(delta, cmd_flags=None, dev=None, divisor=1000, nslots=27, ca
 
 
 # ------------------------------------------------------------------------------------
+# block-I/O request pairing
+# ------------------------------------------------------------------------------------
+def req_join_tile():
+    """igx_req_join_tile: rows per tile of the join's device scan (host call, no GPU)."""
+    return int(_abi.lib().igx_req_join_tile())
+
+
+def req_join(req, kind, ts, valid=None, pend_cap=None, sync=True):
+    """igx_req_join: the start / issue / done join of block-I/O probe rows by request pointer
+    (biotop.bpf.c:41-130, biolatency.bpf.c:47-154; the contract is in include/igx.h).
+    req, ts: u64 (or int64) device tensors, kind and valid: uint8, all of n rows in stream order.
+    Returns a dict: done, issue, who (int32 row ids; who is -1, i.e. IGX_NO_COL, without a START
+    entry), delta (uint64, ts[done] - ts[issue] mod 2^64), one entry per emitting DONE in stream
+    order; pend, the START / ISSUE rows still live at the end, in stream order (at most pend_cap
+    of them, default n); n_done and n_pend, the true counts.  sync=True reads the counts (one
+    host read) and trims the tensors; sync=False returns full-capacity tensors and the counts as
+    device u64 tensors."""
+    torch = torch_mod()
+    ctx = context()
+    n = int(req.numel())
+    cap = n if pend_cap is None else int(pend_cap)
+    dev = req.device
+    req, kind, ts = req.contiguous(), kind.contiguous(), ts.contiguous()
+    valid = None if valid is None else valid.contiguous()
+    m = max(1, n)
+    done, issue, who = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(3))
+    delta = torch.empty(m, dtype=torch.uint64, device=dev)
+    pend = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
+    cnt = torch.empty(2, dtype=torch.uint64, device=dev)
+    ctx.check(ctx.L.igx_req_join(ctx.h, ptr(req), ptr(kind), ptr(ts), ptr(valid), n, ptr(done), ptr(issue),
+                                 ptr(who), ptr(delta), C.c_void_p(cnt.data_ptr()), ptr(pend), cap,
+                                 C.c_void_p(cnt.data_ptr() + 8)))
+    out = {"done": done[:n], "issue": issue[:n], "who": who[:n], "delta": delta[:n], "pend": pend[:cap],
+           "n_done": cnt[0:1], "n_pend": cnt[1:2]}
+    if not sync:
+        return out
+    nd, npend = (int(x) for x in cnt.cpu().view(torch.int64))
+    for k in ("done", "issue", "who", "delta"):
+        out[k] = out[k][:nd]
+    out["pend"] = out["pend"][:min(npend, cap)]
+    out["n_done"], out["n_pend"] = nd, npend
+    return out
+
+
+# ------------------------------------------------------------------------------------
 # data movement either side of the path
 # ------------------------------------------------------------------------------------
 def partition_rows(rows, key_bytes, nparts):

@@ -581,6 +581,81 @@ def rwflag_of(cmd_flags):
     return int((int(cmd_flags) & 0xFF) == REQ_OP_WRITE)
 
 
+def _cat_rows(a, b):
+    """Rows of a, then rows of b (same dtype and row shape).  Unsigned columns are joined
+    through the signed view of the same width."""
+    torch = torch_mod()
+    if a is None or a.shape[0] == 0:
+        return b
+    signed = {torch.uint16: torch.int16, torch.uint32: torch.int32, torch.uint64: torch.int64}.get(b.dtype)
+    if signed is None:
+        return torch.cat([a, b])
+    return torch.cat([a.contiguous().view(signed), b.contiguous().view(signed)]).view(b.dtype)
+
+
+class _ReqCarry:
+    """The in-band state of the request pairing (include/igx.h, igx_req_join): the START /
+    ISSUE rows still live after a batch, every column, put in front of the next batch -- what
+    the reference keeps in its `start` / `whobyreq` maps between probes."""
+
+    def __init__(self, pending_cap):
+        self.pending_cap = pending_cap
+        self.rows = None          # {column: tensor} of the carried rows, in stream order
+
+    def join(self, cols):
+        """cols: {name: device tensor} with req, kind, ts and whatever travels with a row.
+        Returns (all rows with the carry in front, the join's result); keeps the new carry."""
+        if self.rows is not None:
+            cols = {k: _cat_rows(self.rows[k], v) for k, v in cols.items()}
+        j = engine.req_join(cols["req"], cols["kind"], cols["ts"], pend_cap=self.pending_cap)
+        if j["n_pend"] > self.pending_cap:
+            raise _abi.IgxError(_abi.IGX_ENOSPC, f"block-io pairing: {j['n_pend']} requests in flight exceed "
+                                                 f"pending_cap={self.pending_cap}")
+        names = list(cols)
+        self.rows = dict(zip(names, engine.take([cols[k] for k in names], j["pend"])))
+        return cols, j
+
+
+class TopBlockIOProbeTracer(TopBlockIOTracer):
+    """top block-io from its three probes' own rows: blk_account_io_start (kind START, whose
+    mntns / pid / comm are who_t), blk_mq_start_request (ISSUE: ts, data_len) and
+    blk_account_io_done (DONE: ts, cmd_flags, major, minor), paired by request pointer on the
+    device (biotop.bpf.c:41-130) and then counted by TopBlockIOTracer's table unchanged.
+
+    Requests still in flight after a batch are carried into the next one, across nextStats too:
+    the reference's start / whobyreq maps live on while only counts is drained
+    (tracer.go:211-282).  More than pending_cap of them raises IgxError(IGX_ENOSPC).  The carry
+    belongs to the tracer, so StreamingTopTracer, which alternates between two tracers, would
+    split it: feed one tracer."""
+
+    PROBE = ("req", "kind", "ts", "mntns", "pid", "comm", "data_len", "cmd_flags", "major", "minor")
+
+    def __init__(self, pending_cap=1 << 20, **kw):
+        super().__init__(**kw)
+        self._carry = _ReqCarry(pending_cap)
+
+    def feed(self, events: dict, n: Optional[int] = None, base_idx: Optional[int] = None):
+        """events maps PROBE names to device tensors of the batch's rows in stream order."""
+        torch = torch_mod()
+        n = int(events["req"].shape[0]) if n is None else n
+        cols, j = self._carry.join({k: events[k][:n] for k in self.PROBE})
+        nd = j["n_done"]
+        if nd == 0:
+            return
+        mntns, pid, comm = engine.take([cols["mntns"], cols["pid"], cols["comm"]], j["who"], pad=True)
+        data_len, = engine.take([cols["data_len"]], j["issue"])
+        cmd_flags, major, minor = engine.take([cols["cmd_flags"], cols["major"], cols["minor"]], j["done"])
+        # rwflag_of per row (biotop.bpf.c:108)
+        rwflag = ((cmd_flags.view(torch.int32) & 0xFF) == REQ_OP_WRITE).to(torch.int32)
+        super().feed({"mntns": mntns, "pid": pid, "rwflag": rwflag, "major": major, "minor": minor, "comm": comm,
+                      "data_len": data_len, "delta_ns": j["delta"]}, nd, base_idx)
+
+    @property
+    def pending(self):
+        """Requests in flight (rows carried into the next batch)."""
+        return 0 if self._carry.rows is None else int(self._carry.rows["req"].shape[0])
+
+
 # ------------------------------------------------------------------------------------
 # streaming interval mode (SURVEY.md §8(f) row 2)
 # ------------------------------------------------------------------------------------
@@ -776,6 +851,27 @@ class ProfileBlockIOTracer:
             return
         self.hist = engine.hist_log2(dev, cont, delta_ns, self.devs, self.ncont, self.divisor,
                                      MAX_SLOTS, hist=self.hist)
+
+    def feed_probes(self, req, kind, ts, dev=None, cmd_flags=None, pending_cap=1 << 20):
+        """The probes' own rows instead of finished latencies: block_rq_insert / block_rq_issue
+        (kind ISSUE: ts) and block_rq_complete (DONE: ts, and the dev / cmd_flags the key is
+        built from), paired by request pointer on the device (biolatency.bpf.c:47-154), then
+        feed() with the latencies as s64 -- a negative one is dropped there, as the probe's
+        `delta < 0` branch does (:115-117).  Requests in flight are carried to the next call."""
+        torch = torch_mod()
+        if getattr(self, "_carry", None) is None:
+            self._carry = _ReqCarry(pending_cap)
+        cols = {"req": req, "kind": kind, "ts": ts}
+        if dev is not None:
+            cols["dev"] = dev
+        if cmd_flags is not None:
+            cols["cmd_flags"] = cmd_flags
+        cols, j = self._carry.join(cols)
+        if j["n_done"] == 0:
+            return
+        at_done = dict(zip([k for k in ("dev", "cmd_flags") if k in cols],
+                           engine.take([cols[k] for k in ("dev", "cmd_flags") if k in cols], j["done"])))
+        self.feed(j["delta"].view(torch.int64), dev=at_done.get("dev"), cmd_flags=at_done.get("cmd_flags"))
 
     def slots(self):
         """u32 slots per key, host numpy (nkeys, 27); keyed mode: in first-event order."""
