@@ -538,6 +538,75 @@ int igx_req_join(igx_ctx *ctx, const uint64_t *req, const uint8_t *kind, const u
                  uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend);
 int igx_req_join_tile(void);
 
+/* ---- profile cpu: row interning, symbol lookup -------------------------------------------- */
+/* profile cpu (pkg/gadgets/profile/cpu/tracer/bpf/profile.bpf.c:60-114) keys its counts by
+ * key_t (profile.h:9-16), whose two stack fields are ids: bpf_get_stackid (:93, :98) turns a
+ * stack of up to 127 return addresses (1016 bytes) into a small number through the stack map.
+ * igx_intern is that map for any fixed-width row of up to 1 KiB: it reduces a row to a u32 that
+ * can be a group-by key column (group-by keys themselves end at IGX_MAX_KEY_BYTES).
+ *
+ * The object owns a device store of the distinct rows seen so far, over all igx_intern_add
+ * calls.  A row's id is its rank by first appearance in the stream: 0 for the first distinct
+ * row, 1 for the next new one, and so on.  igx_intern_add takes nrows rows of row_bytes at rows
+ * + i * row_stride (device) in stream order and writes out_ids (device, nrows entries): for a
+ * row whose content is stored, that content's id; for a new content, D + r, with D the number
+ * of rows stored before the call and r the number of new contents whose first valid occurrence
+ * in this batch comes before this content's first valid occurrence.  Rows with valid[i] == 0
+ * (valid nullable) get IGX_NO_COL and are not stored.  Equality is over all row_bytes bytes;
+ * callers zero-pad short stacks, as the kernel's stack map does.  So ids are a function of the
+ * stream alone: any split of one stream into batches gives the same ids, whatever the
+ * scheduling.
+ *
+ * Limits (IGX_EINVAL otherwise): row_bytes a multiple of 8 in 8..1024; rows 8-byte aligned;
+ * row_stride a multiple of 8 and at least row_bytes; out_ids 4-byte aligned; capacity in
+ * 1..2^28; nrows <= 2^31 - 1 (0 is valid).  The table has S slots, S a power of two and at
+ * least 2 x capacity (igx_intern_slots).  Memory: capacity x row_bytes for the store, 8 bytes
+ * per slot, and per-call scratch of about 5 bytes per row plus 12 per 1024 rows; device memory
+ * that cannot be had returns IGX_ENOMEM and nothing stays allocated.
+ *
+ * Overflow: when a call would take the distinct count past capacity, that call's ids and
+ * later calls' ids are unspecified (nothing is written out of bounds) and igx_intern_count
+ * returns IGX_ENOSPC from then on.  The reference's max_entries (256 stacks, 10240 keys:
+ * profile.bpf.c:17-30) and the stack map's bucket-collision -EEXIST are kernel artifacts and
+ * are not reproduced.
+ *
+ * igx_intern_count (synchronises): the number of distinct rows stored.  igx_intern_rows
+ * (asynchronous gather): out (device, 8-byte aligned) receives k rows of row_bytes, row j the
+ * content of ids[j] (device, 4-byte aligned); an id of IGX_NO_COL, or one at or above the
+ * distinct count, yields a zero row.  igx_intern_slots (host): S.
+ *
+ * igx_intern_hash_rows (host only, no GPU): out[i] = the 64-bit hash of the row at rows +
+ * i * row_stride, the function the kernels use (csrc/k_stack.h compiles for both sides).  A
+ * row's home slot is hash & (S - 1), probing is linear from there, and a slot carries the tag
+ * hash >> 32: a candidate row is compared only where the tags agree.  Rows equal in both and
+ * different in content are the table's worst case, and these two statements let a caller build
+ * them. */
+typedef struct igx_intern igx_intern;
+int igx_intern_create(igx_ctx *ctx, uint32_t row_bytes, uint64_t capacity, igx_intern **out);
+int igx_intern_add(igx_intern *t, const void *rows, uint64_t row_stride, const uint8_t *valid /*nullable*/,
+                   uint64_t nrows, uint32_t *out_ids);
+int igx_intern_count(igx_intern *t, uint64_t *n_distinct);
+int igx_intern_rows(igx_intern *t, const uint32_t *ids, uint64_t k, void *out);
+int igx_intern_slots(igx_intern *t, uint64_t *n_slots);
+int igx_intern_destroy(igx_intern *t);
+int igx_intern_hash_rows(const void *rows, uint32_t row_bytes, uint64_t row_stride, uint64_t n, uint64_t *out);
+
+/* findKernelSymbol (pkg/gadgets/profile/cpu/tracer/tracer.go:184-208) for n addresses:
+ * out_idx[i] (device u32) is the index into the symbol table of the symbol ips[i] resolves to,
+ * or IGX_NO_COL for "[unknown]".  sym_addr (device, nsyms u64) is the table in the order given
+ * (readKernelSymbols, :139-177, does not sort /proc/kallsyms and neither does this).  Exactly
+ * as written:
+ *   start = 0, end = nsyms - 1 (signed), addr = 0
+ *   while start < end: mid = start + (end - start + 1) / 2; addr = sym[mid];
+ *                      if addr <= ip: start = mid, else end = mid - 1
+ *   the result is start if start == end && sym[start] <= addr
+ * The last comparison is against addr, the last address probed, not against ip.  So in a sorted
+ * table of two or more symbols an ip below every symbol still resolves to symbol 0, and a
+ * one-symbol table resolves only if that symbol's address is 0.  nsyms <= 2^32 - 2; sym_addr
+ * and ips 8-byte aligned, out_idx 4-byte aligned (IGX_EINVAL otherwise).  Asynchronous. */
+int igx_ksym_lookup(igx_ctx *ctx, const uint64_t *sym_addr, uint64_t nsyms,
+                    const uint64_t *ips, uint64_t n, uint32_t *out_idx);
+
 /* ---- group:sum of float columns, IP text --------------------------------------------- */
 /* GroupEntries' float group:sum (group.go:133-156, flattenValues): perm (device u32, n) is a
  * stable sort of the rows by the group key (key_bytes at row * key_stride of keys); each run

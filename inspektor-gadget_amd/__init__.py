@@ -1,7 +1,7 @@
 """igx: MI355X-native event aggregation for Inspektor Gadget's hot path.
 
 Mirrors the reference's pkg/columns (filter / sort / group), pkg/gadgets/top and the
-keyed aggregations behind top tcp/file/block-io, profile block-io and advise
+keyed aggregations behind top tcp/file/block-io, profile block-io/cpu and advise
 network-policy.  All event work runs in libigx.so (HIP kernels for gfx950) through the C
 ABI declared in include/igx.h; torch supplies device memory, streams and RCCL.
 

@@ -163,6 +163,14 @@ SIGNATURES = [
     ("igx_log2_slots", _I, [_VP, _VP, _U64, _U64, _U32, _VP, _VP]),
     ("igx_req_join", _I, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _VP, _VP, _VP, _U64, _VP]),
     ("igx_req_join_tile", _I, []),
+    ("igx_intern_create", _I, [_VP, _U32, _U64, C.POINTER(_VP)]),
+    ("igx_intern_add", _I, [_VP, _VP, _U64, _VP, _U64, _VP]),
+    ("igx_intern_count", _I, [_VP, C.POINTER(_U64)]),
+    ("igx_intern_rows", _I, [_VP, _VP, _U64, _VP]),
+    ("igx_intern_slots", _I, [_VP, C.POINTER(_U64)]),
+    ("igx_intern_destroy", _I, [_VP]),
+    ("igx_intern_hash_rows", _I, [_VP, _U32, _U64, _U64, _VP]),
+    ("igx_ksym_lookup", _I, [_VP, _VP, _U64, _VP, _U64, _VP]),
     ("igx_partition_rows", _I, [_VP, _VP, _U64, _U32, _U32, _U32, _VP, _VP]),
     ("igx_partition_groups", _I, [_VP, _VP, _VP, _U32, _VP, _U64, _VP]),
     ("igx_dist_get_unique_id", _I, [_VP]),

@@ -547,6 +547,113 @@ def req_join(req, kind, ts, valid=None, pend_cap=None, sync=True):
 
 
 # ------------------------------------------------------------------------------------
+# profile cpu: row interning, kernel symbol lookup
+# ------------------------------------------------------------------------------------
+def _row_view(rows, row_bytes):
+    """(pointer, stride in bytes, n) of a 2-D device tensor whose rows hold row_bytes bytes."""
+    if rows.dim() != 2 or rows.shape[1] * rows.element_size() != row_bytes:
+        raise ValueError(f"rows must be (n, {row_bytes} bytes)")
+    if rows.shape[0] > 1 and rows.stride(1) != 1:
+        rows = rows.contiguous()
+    stride = rows.stride(0) * rows.element_size() if rows.shape[0] > 1 else row_bytes
+    return rows, stride, int(rows.shape[0])
+
+
+class Interner:
+    """igx_intern: fixed-width rows of up to 1 KiB -> u32 ids by first appearance in the stream
+    (what bpf_get_stackid and the stack map do for profile cpu; the contract is in
+    include/igx.h).  rows are 2-D device tensors of row_bytes bytes per row (a row stride larger
+    than that is passed through)."""
+
+    def __init__(self, row_bytes, capacity, ctx=None):
+        self.ctx = context() if ctx is None else ctx
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.L.igx_intern_create(self.ctx.h, row_bytes, capacity, C.byref(h)))
+        self.h = h
+        self.row_bytes, self.capacity = row_bytes, capacity
+
+    def add(self, rows, valid=None):
+        """igx_intern_add (asynchronous): int32 ids of the rows (-1, i.e. IGX_NO_COL, where
+        valid is 0)."""
+        torch = torch_mod()
+        self.ctx.bind_stream()
+        rows, stride, n = _row_view(rows, self.row_bytes)
+        valid = None if valid is None else valid.contiguous()
+        out = torch.empty(max(1, n), dtype=torch.int32, device=rows.device)
+        self.ctx.check(self.ctx.L.igx_intern_add(self.h, ptr(rows), stride, ptr(valid), n, ptr(out)))
+        return out[:n]
+
+    def count(self):
+        """igx_intern_count (synchronises): distinct rows stored; IgxError(IGX_ENOSPC) once the
+        capacity has overflowed."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.L.igx_intern_count(self.h, C.byref(n)))
+        return n.value
+
+    def slots(self):
+        """igx_intern_slots (host): S."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.L.igx_intern_slots(self.h, C.byref(n)))
+        return n.value
+
+    def rows(self, ids):
+        """igx_intern_rows (asynchronous): uint8 (k, row_bytes), the content of each id; zero
+        rows for IGX_NO_COL and ids at or above the distinct count."""
+        torch = torch_mod()
+        self.ctx.bind_stream()
+        if ids.dtype not in (torch.int32, torch.uint32):
+            ids = ids.to(torch.int32)
+        ids = ids.contiguous()
+        k = int(ids.numel())
+        out = torch.empty((max(1, k), self.row_bytes), dtype=torch.uint8, device=ids.device)
+        self.ctx.check(self.ctx.L.igx_intern_rows(self.h, ptr(ids), k, ptr(out)))
+        return out[:k]
+
+    def destroy(self):
+        if self.h:
+            self.ctx.L.igx_intern_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def intern_hash_rows(rows, row_bytes=None, row_stride=None):
+    """igx_intern_hash_rows (host, no GPU): the interner's 64-bit row hash of a C-contiguous
+    numpy array of rows (row_bytes defaults to the row's bytes, row_stride to the array's)."""
+    import numpy as np
+    rows = np.ascontiguousarray(rows)
+    if rows.ndim != 2:
+        raise ValueError("rows must be 2-D")
+    stride = rows.strides[0] if row_stride is None else row_stride
+    rb = rows.shape[1] * rows.itemsize if row_bytes is None else row_bytes
+    out = np.empty(rows.shape[0], np.uint64)
+    rc = _abi.lib().igx_intern_hash_rows(rows.ctypes.data_as(C.c_void_p), rb, stride, rows.shape[0],
+                                          out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise IgxError(rc, "igx_intern_hash_rows: bad row_bytes / row_stride")
+    return out
+
+
+def ksym_lookup(sym_addr, ips):
+    """igx_ksym_lookup: findKernelSymbol (profile/cpu/tracer/tracer.go:184-208) of every
+    address of ips (u64 device tensor, any shape) over the table sym_addr (u64 device tensor, in
+    the order given).  Returns int32 symbol indices of ips' shape, -1 (IGX_NO_COL) for
+    "[unknown]"."""
+    torch = torch_mod()
+    ctx = context()
+    ips = ips.contiguous()
+    sym_addr = sym_addr.contiguous()
+    n = int(ips.numel())
+    out = torch.empty(max(1, n), dtype=torch.int32, device=ips.device)
+    ctx.check(ctx.L.igx_ksym_lookup(ctx.h, ptr(sym_addr), int(sym_addr.numel()), ptr(ips), n, ptr(out)))
+    return out[:n].reshape(ips.shape)
+
+
+# ------------------------------------------------------------------------------------
 # data movement either side of the path
 # ------------------------------------------------------------------------------------
 def partition_rows(rows, key_bytes, nparts):

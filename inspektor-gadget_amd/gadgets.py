@@ -1,5 +1,5 @@
 """The aggregation gadgets as their tracers expose them: top tcp / file / block-io and
-profile block-io, on top of libigx.so.
+profile block-io / cpu, on top of libigx.so.
 
 Each `Top*` class is the user-space half of a reference tracer plus the BPF map update it
 drains, re-cut for batches of events resident in HBM:
@@ -21,6 +21,8 @@ References (paths under the reference root):
                 types/types.go:31-65
   profile block-io  pkg/gadgets/profile/block-io/tracer/tracer.go:56-90 (getReport),
                 tracer/gadget.go:85-143 (reportToString), bpf/biolatency.bpf.c:100-154
+  profile cpu   pkg/gadgets/profile/cpu/tracer/bpf/profile.bpf.c:60-114, tracer/tracer.go:86-322,
+                types/types.go:27-56
 
 The reference's pre-sort order (BPF hash iteration) is replaced by each group's first
 event index; everything else -- keys, wrap widths, sort order including
@@ -896,3 +898,156 @@ class ProfileBlockIOTracer:
     def Stop(self) -> str:
         """tracer.go:92-113: json.Marshal(getReport(...))."""
         return self.getReport().to_json()
+
+
+# ------------------------------------------------------------------------------------
+# profile cpu
+# ------------------------------------------------------------------------------------
+PERF_MAX_STACK_DEPTH = 127      # profile/cpu/tracer/tracer.go:57
+UNKNOWN_SYMBOL = "[unknown]"    # tracer.go:207, :239
+
+
+@dataclass
+class CpuReport:
+    """profile/cpu/types/types.go:27-37 (CommonData: pkg/types/types.go:73-87)."""
+    Node: str = ""
+    Namespace: str = ""
+    Pod: str = ""
+    Container: str = ""
+    Comm: str = ""
+    Pid: int = 0
+    UserStack: List[str] = field(default_factory=list)
+    KernelStack: List[str] = field(default_factory=list)
+    Count: int = 0
+    MntnsID: int = 0             # `json:"-"`
+    FirstIndex: int = 0          # canonical pre-sort position (not in the reference struct)
+
+    def ExtraLines(self) -> List[str]:
+        """types.go:47-56: the kernel stack, then the user stack, innermost frame last."""
+        return (["\t" + s for s in reversed(self.KernelStack)] +
+                ["\t" + s for s in reversed(self.UserStack)])
+
+    def to_json(self) -> str:
+        """json.Marshal(report): every field is omitempty, and an empty slice is empty."""
+        import dataclasses
+        from . import textcolumns as T
+        view = dataclasses.replace(self, UserStack=self.UserStack or None, KernelStack=self.KernelStack or None)
+        return T.marshal(view, _CPU_JSON)
+
+
+_CPU_JSON = _COMMON_JSON[:4] + [("Comm", "comm", True), ("Pid", "pid", True), ("UserStack", "userStack", True),
+                                ("KernelStack", "kernelStack", True), ("Count", "count", True)]
+
+
+def readKernelSymbols(text: str):
+    """tracer.go:139-177 over the text of /proc/kallsyms: [(addr, name)] in file order.  Lines
+    with fewer than three fields are skipped; a first field that strconv.ParseUint(s, 16, 64)
+    rejects is an error."""
+    out = []
+    for line in text.splitlines():
+        fields = line.split()
+        if len(fields) < 3:
+            continue
+        a = fields[0]
+        if any(c not in "0123456789abcdefABCDEF" for c in a) or int(a, 16) >> 64:
+            raise ValueError(f'strconv.ParseUint: parsing "{a}": invalid syntax')
+        out.append((int(a, 16), fields[2]))
+    return out
+
+
+class ProfileCpuTracer:
+    """profile cpu: ig_prof_cpu (profile.bpf.c:60-114) over batches of samples, and
+    collectResult (tracer.go:293-322).
+
+    The stack map is an engine.Interner (one for kernel and user stacks, as one `stackmap`
+    serves both bpf_get_stackid calls; kernel rows are added before user rows in each feed), the
+    counts map a device table keyed by key_t (profile.h:9-16).  max_stacks and capacity bound
+    the distinct stacks and keys (IgxError(IGX_ENOSPC) past them); the reference's max_entries
+    and the stack map's -EEXIST are not modelled, nor is filter_by_mnt_ns.
+
+    kallsyms: [(addr, name)] or the text of /proc/kallsyms (readKernelSymbols), in file order."""
+
+    def __init__(self, user_stack_only=False, kernel_stack_only=False, include_idle=False,
+                 depth=PERF_MAX_STACK_DEPTH, max_stacks=1 << 16, capacity=1 << 16, kallsyms=None, ctx=None):
+        import numpy as np
+        from .columns import to_device
+        self.user_stack_only, self.kernel_stack_only = bool(user_stack_only), bool(kernel_stack_only)
+        self.include_idle = bool(include_idle)
+        self.depth = depth
+        syms = readKernelSymbols(kallsyms) if isinstance(kallsyms, str) else list(kallsyms or [])
+        self.sym_names = [name for _, name in syms]
+        self.sym_addr = to_device(np.array([a for a, _ in syms], dtype=np.uint64))
+        self.stacks = engine.Interner(depth * 8, max_stacks, ctx=ctx)
+        # key_t: kernel_ip u64, mntns_id u64, pid u32, user_stack_id i32, kern_stack_id i32, name[16]
+        self.table = engine.Table([8, 8, 4, 4, 4, 16], [_abi.Agg(_abi.AGG_COUNT, 0, _abi.NO_COL, 8, 0)], capacity,
+                                  ctx=ctx)
+        self.next_idx = 0
+
+    def _stack_ids(self, off, keep, stack, status):
+        """profile.bpf.c:90-98: -1 when the other side only was asked for, the error
+        bpf_get_stackid returned, or the stack's id."""
+        torch = torch_mod()
+        if off:
+            return torch.full_like(status, -1)
+        ok = keep & (status >= 0)
+        ids = self.stacks.add(stack.view(torch.uint8).reshape(stack.shape[0], -1), ok.to(torch.uint8))
+        return torch.where(status < 0, status, ids)
+
+    def feed(self, pid, tid, mntns, comm, ip, kstack, kstatus, ustack, ustatus):
+        """One batch of samples as device columns: pid, tid u32; mntns, ip u64; comm (n, 16)
+        uint8; kstack, ustack (n, depth) u64, zero-padded; kstatus, ustatus int32 (>= 0: the
+        stack walk succeeded, < 0: the error bpf_get_stackid returned)."""
+        torch = torch_mod()
+        n = int(pid.shape[0])
+        if n == 0:
+            return
+        keep = torch.ones(n, dtype=torch.bool, device=pid.device) if self.include_idle else \
+            tid.view(torch.int32) != 0                                    # :72-73
+        ks = self._stack_ids(self.user_stack_only, keep, kstack, kstatus.view(torch.int32))
+        us = self._stack_ids(self.kernel_stack_only, keep, ustack, ustatus.view(torch.int32))
+        ip64 = ip.view(torch.int64)
+        kernel_ip = torch.where((ks >= 0) & (ip64 < 0), ip64, torch.zeros_like(ip64))   # :100-107
+        cols = [kernel_ip.view(torch.uint64), mntns, pid, us, ks, comm]
+        self.table.update(cols, list(range(6)), n, self.next_idx, valid=keep.to(torch.uint8))
+        self.next_idx += n
+
+    def reports(self) -> List[CpuReport]:
+        """collectResult: one report per key, ascending count (ties: first occurrence)."""
+        import numpy as np
+        from .columns import to_device
+        torch = torch_mod()
+        self.stacks.count()          # IGX_ENOSPC if the stack map overflowed
+        fin = self.table.finalize()
+        G = fin["n_groups"]
+        if not G:
+            return []
+        rows = host(self.table.gather(self.table.sort([(_abi.TSRC_AGG, 0, False)], G)))
+        f = lambda o, dt: np.ascontiguousarray(rows[:, o:o + np.dtype(dt).itemsize]).view(dt).ravel()   # noqa: E731
+        mntns, pid, us, ks = f(8, np.uint64), f(16, np.uint32), f(20, np.int32), f(24, np.int32)
+        count, first = f(44, np.uint64), f(52, np.uint64)
+        ustacks, kstacks = {}, {}
+        uid = np.unique(us[us >= 0])
+        if len(uid):
+            st = host(self.stacks.rows(to_device(uid.astype(np.int32)))).view(np.uint64)
+            for i, row in zip(uid, st):
+                z = np.flatnonzero(row == 0)
+                ustacks[int(i)] = [UNKNOWN_SYMBOL] * int(z[0] if len(z) else len(row))
+        kid = np.unique(ks[ks >= 0])
+        if len(kid):
+            frames = self.stacks.rows(to_device(kid.astype(np.int32))).view(torch.uint64)
+            idx = host(engine.ksym_lookup(self.sym_addr, frames))
+            for i, row, sym in zip(kid, host(frames), idx):
+                z = np.flatnonzero(row == 0)
+                kstacks[int(i)] = [UNKNOWN_SYMBOL if j < 0 else self.sym_names[j]
+                                   for j in sym[:int(z[0] if len(z) else len(row))]]
+        return [CpuReport(Comm=FromCString(rows[i, 28:44]), Pid=int(pid[i]), UserStack=list(ustacks.get(int(us[i]), [])),
+                          KernelStack=list(kstacks.get(int(ks[i]), [])), Count=int(count[i]), MntnsID=int(mntns[i]),
+                          FirstIndex=int(first[i])) for i in range(G)]
+
+    def Stop(self) -> str:
+        """tracer.go:266-274, :321: json.Marshal([]Report)."""
+        return "[" + ",".join(r.to_json() for r in self.reports()) + "]"
+
+    def destroy(self):
+        self.table.destroy()
+        self.stacks.destroy()

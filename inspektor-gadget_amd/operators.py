@@ -13,7 +13,7 @@ local runtime, so the GPU gadgets are registered and run the way the reference's
   sort, interval 1)
 
 The registered gadgets are the top tracers of gadgets.py (tcp, file, block-io: interval
-gadgets whose maps live in device tables) and profile block-io (a result gadget).  A gadget
+gadgets whose maps live in device tables) and profile block-io / cpu (result gadgets).  A gadget
 instance reads its events from a source callable (`events(interval) -> list of batches`,
 the stand-in for the kernel probes); each interval runs the device group-by, SortStats and
 truncation, then hands the []*Stats to the parser chain: operator enrichment, MatchAll and
@@ -412,9 +412,10 @@ def _sortable_params(sort_default):
 class GadgetDesc:
     """A registered GPU gadget (GadgetDesc + GadgetInstantiate)."""
 
-    def __init__(self, name, category, typ, description, tracer_cls=None, output=None):
+    def __init__(self, name, category, typ, description, tracer_cls=None, output=None, instance_cls=None):
         self._name, self._category, self._type, self._description = name, category, typ, description
         self.tracer_cls, self.output = tracer_cls, output
+        self.instance_cls = instance_cls   # a result gadget: its PARAMS and RunWithResult
 
     def Name(self):
         return self._name
@@ -431,7 +432,7 @@ class GadgetDesc:
     def ParamDescs(self):
         if self.tracer_cls is not None:
             return _sortable_params(self.tracer_cls.SortByDefault)
-        return {}
+        return {p["Key"]: p["DefaultValue"] for p in getattr(self.instance_cls, "PARAMS", ())}
 
     def Parser(self):
         if self.output is None:
@@ -439,12 +440,14 @@ class GadgetDesc:
         return StatsParser(self.output, self.tracer_cls.STATS_COLS)
 
     def EventPrototype(self):
+        if getattr(self.instance_cls, "PROTOTYPE", None) is not None:
+            return self.instance_cls.PROTOTYPE()
         return {"tcp": _g.TcpStats, "file": _g.FileStats, "block-io": _g.BlockIOStats}.get(self.output, dict)()
 
     def NewInstance(self, params: dict):
         if self.tracer_cls is not None:
             return TopGadgetInstance(self, params)
-        return ProfileBlockIOInstance(params)
+        return (self.instance_cls or ProfileBlockIOInstance)(params)
 
 
 class TopGadgetInstance:
@@ -505,6 +508,45 @@ class ProfileBlockIOInstance:
         return tr.getReport().to_json().encode()
 
 
+class ProfileCpuInstance:
+    """profile cpu as a RunWithResultGadget: every batch of the source (a dict of the sample
+    columns ProfileCpuTracer.feed takes) runs the device probe; the result is Stop()'s JSON
+    array of reports (tracer.go:266-274).  params: user-stack / kernel-stack (gadget.go:26-67),
+    and for the stand-in of the host's state "kallsyms", "include-idle", "depth", "max-stacks",
+    "capacity"."""
+
+    # gadget.go:48-67
+    PARAMS = ({"Key": "user-stack", "Alias": "U", "Title": "User Stack", "DefaultValue": False,
+               "Description": "Show stacks from user space only (no kernel space stacks)", "TypeHint": "bool"},
+              {"Key": "kernel-stack", "Alias": "K", "Title": "Kernel Stack", "DefaultValue": False,
+               "Description": "Show stacks from kernel space only (no user space stacks)", "TypeHint": "bool"})
+    PROTOTYPE = _g.CpuReport
+
+    def __init__(self, params: dict):
+        self.params = params
+
+    def RunWithResult(self, ctx: GadgetContext) -> bytes:
+        p = self.params
+        kw = {k: p[name] for k, name in (("depth", "depth"), ("max_stacks", "max-stacks"), ("capacity", "capacity"))
+              if name in p}
+        tr = _g.ProfileCpuTracer(user_stack_only=bool(p.get("user-stack", False)),
+                                 kernel_stack_only=bool(p.get("kernel-stack", False)),
+                                 include_idle=bool(p.get("include-idle", False)), kallsyms=p.get("kallsyms"), **kw)
+        try:
+            source = p.get("events")
+            i = 0
+            while source is not None:
+                batches = source(i)
+                if batches is None:
+                    break
+                for b in batches:
+                    tr.feed(**b)
+                i += 1
+            return tr.Stop().encode()
+        finally:
+            tr.destroy()
+
+
 def _register_builtin():
     Register(GadgetDesc("tcp", "top", TypeTraceIntervals, "Periodically report TCP activity",
                         _g.TopTcpTracer, "tcp"))
@@ -514,6 +556,8 @@ def _register_builtin():
                         _g.TopBlockIOTracer, "block-io"))
     Register(GadgetDesc("block-io", "profile", TypeProfile, "Analyze block I/O performance through a latency "
                         "distribution"))
+    Register(GadgetDesc("cpu", "profile", TypeProfile, "Analyze CPU performance by sampling stack traces",
+                        instance_cls=ProfileCpuInstance))
 
 
 _register_builtin()
