@@ -1,6 +1,8 @@
 // k_groupby_part.h -- the partitioned form of the group-by (kernel (2) for high-cardinality
-// streams).  Included by k_groupby.hip inside its anonymous namespace: it uses GbArgs, the
-// row decoders, the key hash and the HBM table's claim protocol defined there.
+// streams): its device code.  Included by k_gb_part.hip (passes K, O, S, A, B: it instantiates
+// them and holds the plain kernels and the plan) and by k_gb_part_c.hip (pass C), each inside its
+// anonymous namespace.  It uses GbArgs, the row decoders, the key hash and the HBM table's claim
+// protocol of k_gb_table.h, and PartArgs and the form's constants of k_gb_part.h.
 //
 // Reference semantics are those of k_groupby (the top gadgets' BPF maps, GeneratePolicies'
 // first-event-wins map, advisor.go:279-320): exact keys, wrapped sums, first event index.
@@ -32,73 +34,6 @@
 //      the table's CAS claims and atomics.
 // HBM bytes per kept row: the key columns read twice (K, A), the loaded columns once, and
 // one record written and read back twice (A -> B -> C); per group one probe of its region.
-
-constexpr uint32_t PTA = 256;                  // threads per block of passes K, A and B
-constexpr uint32_t PTC = 512;                  // ... of the aggregate pass (two blocks per CU)
-constexpr size_t PART_TILE_LDS = 72 * 1024;    // a B tile: records + 6 B each
-constexpr size_t PART_AGG_LDS = 80 * 1024;     // the C block: LDS table + one round of records
-constexpr uint32_t PART_LB_MAX = 15;           // final buckets <= 2^15 (count-pass LDS histogram)
-constexpr uint32_t PART_F_MAX = 256;           // buckets per scatter level (one per thread)
-constexpr uint32_t PNV = 2 * AMAX;             // distinct value / condition columns a record carries
-constexpr uint32_t CHT = 64;                   // A tiles per chunk of the offset scan
-constexpr uint32_t RC1_PAD = 16;               // words between two slice cursors of pass A
-constexpr uint32_t PART_S1_LOG = 3;            // slices per first-level region (regions)
-constexpr uint32_t PART_U1_MAX = PART_F_MAX << PART_S1_LOG;
-
-struct PartArgs {
-    uint32_t *recs1, *recs2;   // records after pass A / pass B (rq quads each)
-    uint32_t *cnt1;            // tiles_a x F1: an A tile's rows per first-level bucket, then the
-                               // exact output position of that run (pass O)
-    uint32_t *csum;            // nchunk x F1: the same per chunk of CHT A tiles
-    uint32_t *hist;            // NB: rows per final bucket (pass K)
-    uint32_t *start2;          // NB + 1: first record of each final bucket (prefix of hist)
-    uint32_t *cur2;            // NB: pass B's write cursors (final buckets)
-    uint32_t *tstart;          // F1 + 1 (regions: U1 + 1): first B tile of each first-level bucket
-                               // (regions: of each slice)
-    uint32_t *bt;              // B tile -> first-level bucket
-    uint32_t *istart;          // NB + 1: first C work item of each final bucket
-    uint32_t *itfb;            // C work item -> final bucket
-    uint32_t *ctl;             // [0] C work-item dequeue, [1] B tiles, [2] C work items
-    // the row's value / condition columns, each loaded once (aggregates sharing a column
-    // share it): pointer, width (0 = unused: dword 0 of a readable column) and high-dword
-    // offset (4 for 8-byte columns)
-    const uint8_t *vcol[PNV];
-    uint32_t vcw[PNV], vchi[PNV];
-    uint32_t rpos[PNV], rw2[PNV];      // record word of column j's raw value (+1 when 8 bytes)
-    uint32_t nv;                       // loaded columns
-    uint32_t vsrc[AMAX], csrc[AMAX];   // column of aggregate x's value / condition (PNV = none)
-    uint32_t avp[AMAX], acp[AMAX];     // ... its record word (0xFFFF = none) ...
-    uint32_t av2[AMAX], ac2[AMAX];     // ... and 1 when it is 8 bytes wide
-    uint32_t tiles_a, nchunk;  // A tiles (PTA x rows-per-thread rows each), chunks of CHT tiles
-    uint32_t trb;              // records per B tile
-    uint32_t f1, f2, lb;       // bucket bits of the two levels, lb = f1 + f2
-    uint32_t sb_log;           // log2 table slots per final bucket
-    uint32_t occw;             // occupancy bitmap words per final bucket (slots / 32)
-    uint32_t rq, rq_magic;     // record quads (16 B); ceil(2^32 / rq) for quad -> record
-    uint32_t kpw[KWMAX];       // key word w lives in record word kpw[w] ...
-    uint32_t ksh[KWMAX];       // ... at this bit shift (1- and 2-byte columns share words)
-    uint32_t kmsk[KWMAX];      // ... with this mask (0 = a padding word)
-    uint32_t kpn;              // packed key words
-    uint32_t iw, ipos;         // index words (1 = row offset, 2 = global index column) and their word
-    uint32_t ch;               // records per C work item (larger buckets are split)
-    uint32_t E;                // LDS table entries
-    uint32_t uc;               // records per thread and round of pass C
-    uint32_t maxp;             // LDS probes before a row takes the HBM path
-    uint32_t combine;          // wave pre-combine rounds per 64 records (0 = off)
-    uint32_t dbg;              // diagnostics (IGX_GBP_DEBUG): phases to skip, results invalid
-    // region variant (no count pass): bucket b's records fill a fixed region of reg records
-    // through a cursor (one atomic per (tile, bucket)); a record past its region merges into
-    // the table directly (find-or-insert + atomics: exact on any stream)
-    // Pass A's cursors are the most contended words of the form (every A tile adds to each of
-    // the F1): a first-level region is cut into 2^s1log slices, A tile t fills slice
-    // t mod 2^s1log, and each slice's cursor has a 64-B line of its own (RC1_PAD words)
-    uint32_t *rc1, *rc2;       // U1 = F1 << s1log slice cursors (stride RC1_PAD) / NB final-region
-                               // cursors (records reserved; may pass the region)
-    uint32_t reg1, reg2;       // records per first-level slice / final region (0: exact runs)
-    uint32_t s1log;            // log2 slices per first-level region (0 in the exact form)
-    uint32_t c2pad;            // words between two final-region cursors (rc2)
-    uint32_t pe;               // pass C keeps 16-B packed entries (distinct-only, see c_row_pe)
-};
 
 // record words (compile-time bound): packed key words, loaded columns, index
 template <int KW, int NV>
@@ -301,19 +236,6 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t *wsum, 
     return r;
 }
 
-// Fused predicates of an update in the partitioned form: evaluated once into a row mask
-// (AND-ed with the nil mask), which the passes then read like `valid`.
-__global__ __launch_bounds__(256) void k_gbp_mask(GbArgs a, uint8_t *out) {
-    for (uint64_t row = (uint64_t)blockIdx.x * 256 + threadIdx.x; row < a.n; row += (uint64_t)gridDim.x * 256) {
-        bool ok = !a.valid || a.valid[row] != 0;
-        for (uint32_t q = 0; q < a.npred && q < PMAX; ++q)
-            ok = ok && ((a.gwidth[q] && ld_val(a.gptr[q], row, a.gwidth[q]) != a.gref[q]) ||
-                        pred_scalar(ld_val(a.pptr[q], row, a.pwidth[q]), a.pref[q], a.pwidth[q], a.pkind[q],
-                                    a.pcmp[q], a.pneg[q], a.pcnt[q]));
-        out[row] = ok ? 1 : 0;
-    }
-}
-
 // ---- K: rows per final bucket, and per (A tile, first-level bucket) -------------------------
 // Same tiling as pass A (PTA x R rows per tile), one block per tile.
 template <class L, int NV>
@@ -367,17 +289,9 @@ __device__ __forceinline__ void scan_column(uint32_t *v, uint32_t stride, uint32
     }
 }
 
-// O1: per chunk of CHT A tiles, rows per first-level bucket
-__global__ __launch_bounds__(PTA) void k_gbp_csum(PartArgs p) {
-    const uint32_t F1 = 1u << p.f1, c = blockIdx.x;
-    if (threadIdx.x >= F1) return;
-    const uint32_t t0 = c * CHT, t1 = min(p.tiles_a, t0 + CHT);
-    uint32_t s = 0;
-    for (uint32_t t = t0; t < t1; ++t) s += p.cnt1[(uint64_t)t * F1 + threadIdx.x];
-    p.csum[(uint64_t)c * F1 + threadIdx.x] = s;
-}
-
-// ---- S: bucket starts, cursors, chunk offsets, B tiles, C work items (one block) -----------
+// (the plain kernels of passes O and S and of the region variant -- k_gbp_mask, k_gbp_csum,
+// k_gbp_scan, k_gbp_offs, k_gbr_tiles, k_gbr_items -- are in k_gb_part.hip: a kernel that is no
+// template is emitted by every unit that includes its definition)
 __device__ __forceinline__ uint32_t upper_bound_u32(const uint32_t *v, uint32_t lo, uint32_t hi, uint32_t x) {
     while (lo < hi) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -385,67 +299,6 @@ __device__ __forceinline__ uint32_t upper_bound_u32(const uint32_t *v, uint32_t 
         else hi = mid;
     }
     return lo;
-}
-
-__global__ __launch_bounds__(1024) void k_gbp_scan(PartArgs p) {
-    __shared__ uint32_t wsum[17];
-    __shared__ uint32_t ts[PART_F_MAX + 1];
-    const uint32_t NB = 1u << p.lb, F1 = 1u << p.f1, F2 = 1u << p.f2;
-    const uint32_t per = (NB + 1023) / 1024, b0 = threadIdx.x * per;
-    uint32_t s = 0, si = 0;
-    for (uint32_t i = 0; i < per; ++i) {
-        const uint32_t b = b0 + i;
-        const uint32_t c = b < NB ? p.hist[b] : 0u;
-        s += c;
-        si += (c + p.ch - 1) / p.ch;
-    }
-    uint32_t tot, toti;
-    uint32_t run = block_excl_scan(s, wsum, tot);
-    uint32_t runi = block_excl_scan(si, wsum, toti);
-    for (uint32_t i = 0; i < per; ++i) {
-        const uint32_t b = b0 + i;
-        if (b >= NB) break;
-        const uint32_t c = p.hist[b], ni = (c + p.ch - 1) / p.ch;
-        p.start2[b] = run;
-        p.cur2[b] = run;
-        p.istart[b] = runi;
-        for (uint32_t k = 0; k < ni; ++k) p.itfb[runi + k] = b;
-        run += c;
-        runi += ni;
-    }
-    // first-level buckets: record counts, starts (= start2 of their first final bucket),
-    // chunk offsets and B tiles
-    uint32_t c1 = 0;
-    if (threadIdx.x < F1)
-        for (uint32_t b2 = 0; b2 < F2; ++b2) c1 += p.hist[threadIdx.x * F2 + b2];
-    uint32_t tot1, tott;
-    const uint32_t st1 = block_excl_scan(c1, wsum, tot1);
-    const uint32_t nt = (c1 + p.trb - 1) / p.trb;
-    const uint32_t tst = block_excl_scan(nt, wsum, tott);
-    if (threadIdx.x < F1) {
-        scan_column(p.csum + threadIdx.x, F1, p.nchunk, st1);
-        p.tstart[threadIdx.x] = tst;
-        ts[threadIdx.x] = tst;
-    }
-    if (threadIdx.x == 0) {
-        p.start2[NB] = tot;
-        p.istart[NB] = toti;
-        p.tstart[F1] = tott;
-        ts[F1] = tott;
-        p.ctl[0] = 0;
-        p.ctl[1] = tott;
-        p.ctl[2] = toti;
-    }
-    __syncthreads();
-    for (uint32_t t = threadIdx.x; t < tott; t += 1024) p.bt[t] = upper_bound_u32(ts, 0, F1 + 1, t) - 1;
-}
-
-// O2: each A tile's exact output position per first-level bucket (cnt1 in place)
-__global__ __launch_bounds__(PTA) void k_gbp_offs(PartArgs p) {
-    const uint32_t F1 = 1u << p.f1, c = blockIdx.x;
-    if (threadIdx.x >= F1) return;
-    const uint32_t t0 = c * CHT, t1 = min(p.tiles_a, t0 + CHT);
-    scan_column(p.cnt1 + (uint64_t)t0 * F1 + threadIdx.x, F1, t1 - t0, p.csum[(uint64_t)c * F1 + threadIdx.x]);
 }
 
 template <int KW, int NA, bool WIDE = false>
@@ -598,60 +451,6 @@ __global__ __launch_bounds__(PTA) void k_gbp_a(GbArgs a, PartArgs p) {
         else if (g < p.reg1) st_rec<false>(&out[((uint64_t)((b << p.s1log) + sl) * p.reg1 + g) * rq + q], stage[qi]);
         else spill = q == 0;
         if (p.reg1) region_spill<L, WIDE>(a, p, spill, reinterpret_cast<const uint32_t *>(stage + (uint64_t)(live ? j : 0u) * rq));
-    }
-}
-
-// region variant, between A and B: B tiles of each first-level slice (tstart, bt, ctl[1])
-__global__ __launch_bounds__(1024) void k_gbr_tiles(PartArgs p) {
-    __shared__ uint32_t wsum[17];
-    __shared__ uint32_t ts[PART_U1_MAX + 1];
-    const uint32_t U1 = 1u << (p.f1 + p.s1log);
-    const uint32_t per = (U1 + 1023) / 1024, u0 = threadIdx.x * per;
-    uint32_t nt = 0;
-    for (uint32_t i = 0; i < per; ++i)
-        if (u0 + i < U1) nt += (min(p.rc1[(u0 + i) * RC1_PAD], p.reg1) + p.trb - 1) / p.trb;
-    uint32_t tot;
-    uint32_t st = block_excl_scan(nt, wsum, tot);
-    for (uint32_t i = 0; i < per && u0 + i < U1; ++i) {
-        p.tstart[u0 + i] = st;
-        ts[u0 + i] = st;
-        st += (min(p.rc1[(u0 + i) * RC1_PAD], p.reg1) + p.trb - 1) / p.trb;
-    }
-    if (threadIdx.x == 0) {
-        p.tstart[U1] = tot;
-        ts[U1] = tot;
-        p.ctl[1] = tot;
-    }
-    __syncthreads();
-    for (uint32_t t = threadIdx.x; t < tot; t += 1024) p.bt[t] = upper_bound_u32(ts, 0, U1 + 1, t) - 1;
-}
-
-// region variant, after B: C work items from the final regions' fills (a final bucket larger
-// than ch is split)
-__global__ __launch_bounds__(1024) void k_gbr_items(PartArgs p) {
-    __shared__ uint32_t wsum[17];
-    const uint32_t NB = 1u << p.lb;
-    const uint32_t per = (NB + 1023) / 1024, b0 = threadIdx.x * per;
-    uint32_t si = 0;
-    for (uint32_t i = 0; i < per; ++i) {
-        const uint32_t b = b0 + i;
-        const uint32_t c = b < NB ? min(p.rc2[b * p.c2pad], p.reg2) : 0u;
-        si += (c + p.ch - 1) / p.ch;
-    }
-    uint32_t toti;
-    uint32_t runi = block_excl_scan(si, wsum, toti);
-    for (uint32_t i = 0; i < per; ++i) {
-        const uint32_t b = b0 + i;
-        if (b >= NB) break;
-        const uint32_t c = min(p.rc2[b * p.c2pad], p.reg2), ni = (c + p.ch - 1) / p.ch;
-        p.istart[b] = runi;
-        for (uint32_t k = 0; k < ni; ++k) p.itfb[runi + k] = b;
-        runi += ni;
-    }
-    if (threadIdx.x == 0) {
-        p.istart[NB] = toti;
-        p.ctl[0] = 0;
-        p.ctl[2] = toti;
     }
 }
 
@@ -912,7 +711,7 @@ __device__ __forceinline__ int at_find_insert(const AggTab<KW> &T, const uint32_
 }
 
 // one row (or one LDS group) merged into the HBM table with CAS claims and atomics
-// (WIDE: the table's record addressing, k_groupby.hip probe_issue)
+// (WIDE: the table's record addressing, k_gb_table.h probe_issue)
 template <int KW, int NA, bool WIDE>
 __device__ __forceinline__ void hbm_merge(const GbArgs &a, const uint32_t (&k)[KW], uint64_t h,
                                           const uint64_t (&v)[NA], uint64_t first) {

@@ -1,12 +1,12 @@
 """Group-by predicates against the plain reference evaluator (tests/pred_reference.py).
 
 igx_groupby_update evaluates its predicates in three places:
-  fused in the cached / direct forms   row_raw -> assemble -> pred_scalar (k_groupby.hip): up to
+  fused in the cached / direct forms   row_raw -> assemble -> pred_scalar (k_gb_table.h): up to
                                        two scalar comparisons or IN sets on 1/2/4/8-byte columns;
                                        the value is cut out of a loaded dword by (row * width) & 3,
                                        or taken from the SUM's own loaded value (pshare); a guard is
                                        read from an aggregate's condition value (pguard)
-  fused in the partitioned form        k_gbp_mask (k_groupby_part.h): ld_val, the guard from gptr
+  fused in the partitioned form        k_gbp_mask (k_gb_part.hip): ld_val, the guard from gptr
   spilled to the row mask              k_pred_mask -> pred_match (k_common.h): string rules, a third
                                        scalar comparison, a guard on a column that is no aggregate's
                                        condition column (pred_match's gwidth branch)

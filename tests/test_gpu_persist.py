@@ -1,4 +1,4 @@
-"""Keys kept across intervals (igx_groupby_reset's generations, k_groupby.hip header): every
+"""Keys kept across intervals (igx_groupby_reset's generations, k_gb_table.h header): every
 interval's table must still be exactly the reference's per-interval map drain
 (pkg/gadgets/top/file/tracer/tracer.go:148-220, tcp/tracer/tracer.go:147-226) -- the
 interval's own groups, sums and first indices -- while the keys themselves stay in the table.
