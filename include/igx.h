@@ -377,6 +377,19 @@ typedef struct {
     uint64_t gen_keys;   /* ... keys the table's generation held after it (UINT64_MAX: it ended) */
 } igx_groupby_info_t;
 int igx_groupby_info(igx_table *t, igx_groupby_info_t *out);
+/* Row plans: a cached update whose shape -- key layout, aggregates, fused
+ * predicates, no valid mask, no index column, no divisor -- is exactly the one a shipped gadget
+ * builds runs a kernel instance compiled for that shape; any other update, and every update under
+ * IGX_GB_ROWPLAN=0, runs the general kernel.  Results are identical.
+ * igx_groupby_rowplan: the plan the table's last cached update ran: 0 general, 1 top tcp, 2 top file.
+ * igx_groupby_rowplan_match: the plan an update described as for igx_groupby_create and
+ * igx_groupby_update_ex would run, 0 when none (or the description is invalid).  Host only: no
+ * context, no device; column pointers are compared, never read. */
+int igx_groupby_rowplan(igx_table *t);
+int igx_groupby_rowplan_match(const uint32_t *key_widths, uint32_t nkeys, const igx_agg *aggs,
+                              uint32_t naggs, const igx_col *cols, uint32_t ncols,
+                              const uint32_t *key_cols, const igx_pred *preds, uint32_t npreds,
+                              const uint8_t *valid, uint32_t idx_col);
 /* igx_groupby_finalize without its host synchronisation: the occupied-slot list is built on
  * the device and the group count stays there (view->d_n_groups; view->n_groups is 0 until
  * igx_groupby_wait).  igx_groupby_sort's top-K of such a table (0 < k <= 4096, no float or

@@ -146,6 +146,9 @@ SIGNATURES = [
     ("igx_groupby_finalize_async", _I, [_VP, C.POINTER(TableView)]),
     ("igx_groupby_wait", _I, [_VP, C.POINTER(C.c_uint64)]),
     ("igx_groupby_info", _I, [_VP, C.POINTER(GroupbyInfo)]),
+    ("igx_groupby_rowplan", _I, [_VP]),
+    ("igx_groupby_rowplan_match", _I, [C.POINTER(_U32), _U32, C.POINTER(Agg), _U32, C.POINTER(Col), _U32,
+                                       C.POINTER(_U32), C.POINTER(Pred), _U32, _VP, _U32]),
     ("igx_groupby_gather", _I, [_VP, _VP, _U64, _VP]),
     ("igx_groupby_select_ge", _I, [_VP, _U32, _U64, _VP, _U64, _VP]),
     ("igx_groupby_lookup", _I, [_VP, _VP, _U32, _U64, _VP, _VP]),

@@ -861,9 +861,18 @@ __device__ __forceinline__ void prober(const GbArgs &a, const LdsCache<KW> &c, c
 
 // SAMPLE: the same kernel counting the seed sample (seeds_compute), a template instance of its
 // own so that traces and profiles keep its launches apart from the interval's
-template <class L, bool DBG, int NA, bool SAMPLE = false>
+// P: the update's row plan (k_gb_table.h), RowPlanRT for the run-time shape.  The host launches a
+// plan's instance only for an update that matches it field by field (plan_for_update), so what
+// the plan fixes is written over the arguments here and the compiler folds it everywhere.
+template <class L, bool DBG, int NA, bool SAMPLE = false, class P = RowPlanRT>
 __global__ __launch_bounds__(GTB) void k_groupby(GbArgs a) {
     constexpr int KW = L::KW;
+    if constexpr (!P::RT) {
+        static_assert(!DBG && !SAMPLE, "row plans are for the production kernel");
+        a.naggs = P::D.naggs;
+        a.fidx = nullptr;
+        a.dbg = 0;
+    }
     extern __shared__ uint64_t lds[];
     __shared__ uint32_t ring_ctl[8];
     LdsCache<KW> c;
@@ -930,13 +939,13 @@ __global__ __launch_bounds__(GTB) void k_groupby(GbArgs a) {
         uint64_t base = (uint64_t)blockIdx.x * PTB + wave * 64;
         RowRaw<L, NA> R;
         uint32_t nmiss = 0;
-        if (base < a.n) issue_row<L, NA, cached_stream_nt<L>()>(a, min(base + lane, a.n - 1), R);
+        if (base < a.n) issue_row<L, NA, cached_stream_nt<L>(), P>(a, min(base + lane, a.n - 1), R);
         for (; base < a.n; base += stride) {
             const uint64_t row = base + lane;
             uint32_t k[KW];
             uint64_t v[NA];
-            bool ok = decode_row<L, NA>(a, row, R, k, v) && row < a.n;
-            if (base + stride < a.n) issue_row<L, NA, cached_stream_nt<L>()>(a, min(base + stride + lane, a.n - 1), R);
+            bool ok = decode_row<L, NA, P>(a, row, R, k, v) && row < a.n;
+            if (base + stride < a.n) issue_row<L, NA, cached_stream_nt<L>(), P>(a, min(base + stride + lane, a.n - 1), R);
             const uint64_t h = hash_key<KW>(k);
             if (DBG && (a.dbg & 1u)) {   // diagnostics: load + hash only
                 if (ok && h == 0x1234567ull && v[0] == 7) atomicAdd(a.dbg_cnt + 3, 1ull);   // keep live
@@ -1118,17 +1127,17 @@ uint32_t gb_entries_for(uint32_t naggs) {
     return naggs <= 2 ? gb_lds<L, 2>(naggs).E : gb_lds<L, AMAX>(naggs).E;
 }
 
-template <class L, bool DBG, int NA, bool SAMPLE = false>
+template <class L, bool DBG, int NA, bool SAMPLE = false, class P = RowPlanRT>
 void launch_gb_as(igx_ctx *ctx, GbArgs &a, uint32_t blocks) {
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_groupby<L, DBG, NA, SAMPLE>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_groupby<L, DBG, NA, SAMPLE, P>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, GB_LDS_TOTAL);
         attr = true;
     }
     const GbLds g = gb_lds<L, NA>(a.naggs);
     a.lds_entries = g.E;
-    hipLaunchKernelGGL((k_groupby<L, DBG, NA, SAMPLE>), dim3(blocks), dim3(GTB), g.bytes(), ctx->stream, a);
+    hipLaunchKernelGGL((k_groupby<L, DBG, NA, SAMPLE, P>), dim3(blocks), dim3(GTB), g.bytes(), ctx->stream, a);
 }
 
 // k_gb_estimate with the cached kernel's geometry (its E and its GHOST filter)
@@ -1143,11 +1152,23 @@ void launch_estimate_as(igx_ctx *ctx, GbArgs a, uint32_t blocks, uint64_t nsampl
 // The diagnostic variants (IGX_GB_DEBUG) are compiled for the top-tcp key only, so the
 // production kernels carry none of their code.  Tables with at most two aggregates run a
 // kernel that carries two aggregate slots (fewer registers, fewer loads).
+// An update whose shape is a registered row plan's runs that plan's instance (plan: its id from
+// plan_for_update, 0: none or switched off).
 template <class L>
-void launch_gb(igx_ctx *ctx, GbArgs &a, uint32_t blocks) {
+void launch_gb(igx_ctx *ctx, GbArgs &a, uint32_t blocks, int plan) {
     if constexpr (std::is_same<L, StaticLayout<16, 16, 8, 4, 16, 2, 2, 2>>::value) {
         if (a.dbg) {
             launch_gb_as<L, true, 2>(ctx, a, blocks);
+            return;
+        }
+        if (plan == TopTcpPlan::D.id) {
+            launch_gb_as<L, false, 2, false, TopTcpPlan>(ctx, a, blocks);
+            return;
+        }
+    }
+    if constexpr (std::is_same<L, StaticLayout<8, 4, 4, 4>>::value) {
+        if (plan == TopFilePlan::D.id && !a.dbg) {
+            launch_gb_as<L, false, AMAX, false, TopFilePlan>(ctx, a, blocks);
             return;
         }
     }
@@ -1266,7 +1287,9 @@ void gb_cached_load() {
 
 int gb_launch_cached(igx_table *t, GbArgs &a, uint32_t blocks) {
     return gb_with_layout(t, [&](auto tag) {
-        launch_gb<typename decltype(tag)::type>(t->ctx, a, blocks);
+        using L = typename decltype(tag)::type;
+        t->rowplan_last = t->rowplan_on && !a.dbg ? plan_for_update<L>(a) : 0;
+        launch_gb<L>(t->ctx, a, blocks, t->rowplan_last);
         return (int)IGX_OK;
     });
 }

@@ -554,25 +554,131 @@ struct RowRaw {
     uint32_t vraw, plo[PMAX], phi[PMAX], vlo[NA], vhi[NA], clo[NA], chi[NA];
 };
 
-template <class L, int NA, bool NT = true>
-__device__ __forceinline__ void issue_row(const GbArgs &a, uint64_t row, RowRaw<L, NA> &R) {
-    // unconditional loads; slots with nothing to load read dword 0 of the dummy column
-    // (width 0: one cached line for the whole wave)
-    R.vraw = ldd<NT>(a.validp, row * a.validw);
-#pragma unroll
-    for (int p = 0; p < PMAX; ++p) {
-        const uint64_t b = row * a.pldw[p];
-        R.plo[p] = ldd<NT>(a.pptr[p], b);
-        R.phi[p] = ldd<NT>(a.pptr[p], b + a.phioff[p]);
+// ---- row plans -------------------------------------------------------------------------
+// The row pieces below read an update's shape from GbArgs at run time: every column's width,
+// sign, sharing, every predicate's kind and comparison.  A RowPlan fixes that shape at compile
+// time for the plans shipped gadgets build ("Row plans"): an instance over a
+// plan loads each distinct column once, at its own width, loads no dummy column, and evaluates
+// values and predicates with constant widths, kinds and comparisons.  Of GbArgs it reads the
+// column pointers, the reference values (pref, gref, cval) and the table fields; the reference
+// *values* stay run-time.  RowPlanRT is the run-time shape: today's code, unchanged.
+struct PlanAgg {
+    bool count;              // COUNT (adds 1), else SUM of the value column
+    uint8_t vwidth;          // value column bytes (SUM)
+    bool vsign;              // value column is signed
+    bool cond;               // adds only where the condition column holds cval
+    uint8_t cwidth;          // condition column bytes
+    int8_t vshare, cshare;   // the earlier aggregate whose value / condition load it reuses (-1: its own)
+};
+struct PlanPred {
+    uint8_t width, kind, cmp;
+    bool neg;
+    uint8_t cnt;             // reference values of an IN set (else 0)
+    int8_t share;            // the aggregate whose value load it reuses (-1: its own load)
+    int8_t guard;            // the aggregate whose condition value guards it (-1: unguarded)
+};
+struct RowPlanDesc {
+    int id;                  // what igx_groupby_rowplan reports (0 is the run-time shape)
+    int naggs, npred;
+    bool valid, index;       // a valid column / an index column is present
+    PlanAgg agg[AMAX];
+    PlanPred pred[PMAX];
+};
+struct RowPlanRT {
+    static constexpr bool RT = true;
+};
+// gadgets.TopTcpTracer (and the headline benchmark): ip_key_t, sent / received = SUM(size) where
+// dir == 0 / 1, family IN {..} (two 2-byte values), `int copied` (size's memory) > ref where dir == gref
+struct TopTcpPlan {
+    static constexpr bool RT = false;
+    static constexpr RowPlanDesc D = {1, 2, 2, false, false,
+                                      {{false, 4, false, true, 1, -1, -1}, {false, 4, false, true, 1, 0, 0}},
+                                      {{2, IGX_KIND_UINT, IGX_CMP_IN, false, 2, -1, -1},
+                                       {4, IGX_KIND_INT, IGX_CMP_GT, false, 0, 0, 0}}};
+};
+// gadgets.TopFileTracer(AllFiles=True): file_id, reads / rbytes / writes / wbytes = COUNT and
+// SUM(count) where op == 0 / 1, no predicate
+struct TopFilePlan {
+    static constexpr bool RT = false;
+    static constexpr RowPlanDesc D = {2, 4, 0, false, false,
+                                      {{true, 0, false, true, 1, -1, -1}, {false, 4, false, true, 1, -1, 0},
+                                       {true, 0, false, true, 1, -1, 0}, {false, 4, false, true, 1, 1, 0}},
+                                      {}};
+};
+
+// f(std::integral_constant<int, i>) for i in [0, N): loops whose index is a constant expression
+template <class F, size_t... I>
+__device__ __forceinline__ void plan_each(F &f, std::index_sequence<I...>) {
+    (f(std::integral_constant<int, (int)I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void plan_for(F &&f) {
+    plan_each(f, std::make_index_sequence<N>{});
+}
+
+// a plan's column load: W (1, 2, 4 or 8) bytes of the row at their own width, zero-extended into
+// lo (hi: the upper dword of an 8-byte column).  Columns are aligned to their width (plan_aggs,
+// plan_preds), so no shift by the row's phase in a dword is needed.
+template <int W, bool NT>
+__device__ __forceinline__ void plan_ld(const uint8_t *p, uint64_t row, uint32_t &lo, uint32_t &hi) {
+    static_assert(W == 1 || W == 2 || W == 4 || W == 8, "scalar column widths");
+    if constexpr (W == 8) {
+        typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+        const v2u q = stream_ld<NT>(reinterpret_cast<const v2u *>(p) + row);
+        lo = q.x;
+        hi = q.y;
+    } else if constexpr (W == 4) {
+        lo = stream_ld<NT>(reinterpret_cast<const uint32_t *>(p) + row);
+    } else if constexpr (W == 2) {
+        lo = stream_ld<NT>(reinterpret_cast<const uint16_t *>(p) + row);
+    } else {
+        lo = stream_ld<NT>(p + row);
     }
-    L::template load<NT>(a, row, R.k);
+}
+template <int W>
+__device__ __forceinline__ uint64_t plan_val(uint32_t lo, uint32_t hi) {
+    return (uint64_t)lo | (W == 8 ? (uint64_t)hi << 32 : 0ull);
+}
+
+template <class L, int NA, bool NT = true, class P = RowPlanRT>
+__device__ __forceinline__ void issue_row(const GbArgs &a, uint64_t row, RowRaw<L, NA> &R) {
+    if constexpr (!P::RT) {
+        // the plan's distinct columns, each once (the slots it leaves alone are never read)
+        static_assert(P::D.naggs <= NA && !P::D.valid && !P::D.index, "plan does not fit this instance");
+        plan_for<PMAX>([&](auto I) __attribute__((always_inline)) {
+            constexpr int p = decltype(I)::value;
+            if constexpr (p < P::D.npred && P::D.pred[p].share < 0)
+                plan_ld<P::D.pred[p].width, NT>(a.pptr[p], row, R.plo[p], R.phi[p]);
+        });
+        L::template load<NT>(a, row, R.k);
+        plan_for<NA>([&](auto I) __attribute__((always_inline)) {
+            constexpr int x = decltype(I)::value;
+            if constexpr (x < P::D.naggs) {
+                if constexpr (!P::D.agg[x].count && P::D.agg[x].vshare < 0)
+                    plan_ld<P::D.agg[x].vwidth, NT>(a.vptr[x], row, R.vlo[x], R.vhi[x]);
+                if constexpr (P::D.agg[x].cond && P::D.agg[x].cshare < 0)
+                    plan_ld<P::D.agg[x].cwidth, NT>(a.cptr[x], row, R.clo[x], R.chi[x]);
+            }
+        });
+    } else {
+        // unconditional loads; slots with nothing to load read dword 0 of the dummy column
+        // (width 0: one cached line for the whole wave)
+        R.vraw = ldd<NT>(a.validp, row * a.validw);
 #pragma unroll
-    for (int x = 0; x < NA; ++x) {
-        const uint64_t bv = row * a.vldw[x], bc = row * a.cldw[x];
-        R.vlo[x] = ldd<NT>(a.vptr[x], bv);
-        R.vhi[x] = ldd<NT>(a.vptr[x], bv + a.vhioff[x]);
-        R.clo[x] = ldd<NT>(a.cptr[x], bc);
-        R.chi[x] = ldd<NT>(a.cptr[x], bc + a.chioff[x]);
+        for (int p = 0; p < PMAX; ++p) {
+            const uint64_t b = row * a.pldw[p];
+            R.plo[p] = ldd<NT>(a.pptr[p], b);
+            R.phi[p] = ldd<NT>(a.pptr[p], b + a.phioff[p]);
+        }
+        L::template load<NT>(a, row, R.k);
+#pragma unroll
+        for (int x = 0; x < NA; ++x) {
+            const uint64_t bv = row * a.vldw[x], bc = row * a.cldw[x];
+            R.vlo[x] = ldd<NT>(a.vptr[x], bv);
+            R.vhi[x] = ldd<NT>(a.vptr[x], bv + a.vhioff[x]);
+            R.clo[x] = ldd<NT>(a.cptr[x], bc);
+            R.chi[x] = ldd<NT>(a.cptr[x], bc + a.chioff[x]);
+        }
     }
 }
 
@@ -591,18 +697,30 @@ __device__ __forceinline__ void share_raw(const GbArgs &a, uint64_t (&rv)[NA], u
 
 // the value each aggregate adds: 1 (COUNT) or the column's value (sign-extended, divided),
 // 0 when its condition column does not hold cval
-template <int NA>
+template <int NA, class P = RowPlanRT>
 __device__ __forceinline__ void vals_from_raw(const GbArgs &a, const uint64_t (&rv)[NA], const uint64_t (&rc)[NA],
                                               uint64_t (&v)[NA]) {
+    if constexpr (!P::RT) {   // a plan has no divisor
+        plan_for<NA>([&](auto I) __attribute__((always_inline)) {
+            constexpr int x = decltype(I)::value;
+            uint64_t val = 0;
+            if constexpr (x < P::D.naggs) {
+                val = P::D.agg[x].count ? 1ull : (P::D.agg[x].vsign ? sext(rv[x], P::D.agg[x].vwidth) : rv[x]);
+                if (P::D.agg[x].cond && rc[x] != a.cval[x]) val = 0;
+            }
+            v[x] = val;
+        });
+    } else {
 #pragma unroll
-    for (int x = 0; x < NA; ++x) {
-        uint64_t val = 0;
-        if (x < (int)a.naggs) {
-            val = a.vcount[x] ? 1ull : (a.vsign[x] ? sext(rv[x], a.vwidth[x]) : rv[x]);
-            if (a.vdiv[x]) val /= a.vdiv[x];
-            if (a.hascond[x] && rc[x] != a.cval[x]) val = 0;
+        for (int x = 0; x < NA; ++x) {
+            uint64_t val = 0;
+            if (x < (int)a.naggs) {
+                val = a.vcount[x] ? 1ull : (a.vsign[x] ? sext(rv[x], a.vwidth[x]) : rv[x]);
+                if (a.vdiv[x]) val /= a.vdiv[x];
+                if (a.hascond[x] && rc[x] != a.cval[x]) val = 0;
+            }
+            v[x] = val;
         }
-        v[x] = val;
     }
 }
 
@@ -610,11 +728,34 @@ __device__ __forceinline__ void vals_from_raw(const GbArgs &a, const uint64_t (&
 // value / condition column values of its aggregates (an aggregate that shares another's
 // column takes that one's value).  vals_from_raw turns them into the added values; the
 // partitioned form stores the raw values of the loaded columns in its records.
-template <class L, int NA>
+template <class L, int NA, class P = RowPlanRT>
 __device__ __forceinline__ bool row_raw(const GbArgs &a, uint64_t row, const RowRaw<L, NA> &R,
                                         uint32_t (&k)[L::KW], uint64_t (&rv)[NA], uint64_t (&rc)[NA]) {
 #pragma unroll
     for (int w = 0; w < L::KW; ++w) k[w] = R.k[w];
+    if constexpr (!P::RT) {
+        plan_for<NA>([&](auto I) __attribute__((always_inline)) {
+            constexpr int x = decltype(I)::value;
+            rv[x] = rc[x] = 0;
+            if constexpr (x < P::D.naggs) {
+                constexpr PlanAgg g = P::D.agg[x];
+                if constexpr (!g.count) rv[x] = g.vshare >= 0 ? rv[g.vshare < 0 ? 0 : g.vshare] : plan_val<g.vwidth>(R.vlo[x], R.vhi[x]);
+                if constexpr (g.cond) rc[x] = g.cshare >= 0 ? rc[g.cshare < 0 ? 0 : g.cshare] : plan_val<g.cwidth>(R.clo[x], R.chi[x]);
+            }
+        });
+        bool ok = true;
+        plan_for<PMAX>([&](auto I) __attribute__((always_inline)) {
+            constexpr int p = decltype(I)::value;
+            if constexpr (p < P::D.npred) {
+                constexpr PlanPred q = P::D.pred[p];
+                const uint64_t pv = q.share >= 0 ? rv[q.share < 0 ? 0 : q.share] : plan_val<q.width>(R.plo[p], R.phi[p]);
+                bool r = pred_scalar(pv, a.pref[p], q.width, q.kind, q.cmp, q.neg, q.cnt);
+                if constexpr (q.guard >= 0) r = r || rc[q.guard] != a.gref[p];
+                ok = ok && r;
+            }
+        });
+        return ok;
+    }
 #pragma unroll
     for (int x = 0; x < NA; ++x) {
         rv[x] = assemble(R.vlo[x], R.vhi[x], row * a.vwidth[x], a.vwidth[x]);
@@ -639,13 +780,57 @@ __device__ __forceinline__ bool row_raw(const GbArgs &a, uint64_t row, const Row
     return ok;
 }
 
-template <class L, int NA>
+template <class L, int NA, class P = RowPlanRT>
 __device__ __forceinline__ bool decode_row(const GbArgs &a, uint64_t row, const RowRaw<L, NA> &R,
                                            uint32_t (&k)[L::KW], uint64_t (&v)[NA]) {
     uint64_t rv[NA], rc[NA];
-    const bool ok = row_raw<L, NA>(a, row, R, k, rv, rc);
-    vals_from_raw<NA>(a, rv, rc, v);
+    const bool ok = row_raw<L, NA, P>(a, row, R, k, rv, rc);
+    vals_from_raw<NA, P>(a, rv, rc, v);
     return ok;
+}
+
+// ---- the plan registry (host) ------------------------------------------------------------
+// A plan is registered when a shipped gadget builds it.  An update runs a plan's instance only
+// when its GbArgs match the plan field by field: every aggregate's and predicate's shape, the
+// natural packed strides (each column loaded at its own width), no divisor, no valid column and
+// no index column.  Anything else runs the run-time shape.
+inline bool plan_matches(const RowPlanDesc &d, const GbArgs &a) {
+    if ((int)a.naggs != d.naggs || (int)a.npred != d.npred) return false;
+    if ((a.valid != nullptr) != d.valid || (a.fidx != nullptr) != d.index) return false;
+    for (int x = 0; x < d.naggs; ++x) {
+        const PlanAgg &g = d.agg[x];
+        if ((a.vcount[x] != 0) != g.count || (a.hascond[x] != 0) != g.cond || a.vdiv[x]) return false;
+        if (!g.count) {
+            if (a.vwidth[x] != g.vwidth || (a.vsign[x] != 0) != g.vsign) return false;
+            if (a.vshare[x] != (g.vshare < 0 ? (uint32_t)AMAX : (uint32_t)g.vshare)) return false;
+            if (a.vldw[x] != (g.vshare < 0 ? g.vwidth : 0u)) return false;
+        }
+        if (g.cond) {
+            if (a.cwidth[x] != g.cwidth) return false;
+            if (a.cshare[x] != (g.cshare < 0 ? (uint32_t)AMAX : (uint32_t)g.cshare)) return false;
+            if (a.cldw[x] != (g.cshare < 0 ? g.cwidth : 0u)) return false;
+        }
+    }
+    for (int p = 0; p < d.npred; ++p) {
+        const PlanPred &q = d.pred[p];
+        if (a.pwidth[p] != q.width || a.pkind[p] != q.kind || a.pcmp[p] != q.cmp || (a.pneg[p] != 0) != q.neg)
+            return false;
+        if (q.cmp == IGX_CMP_IN && a.pcnt[p] != q.cnt) return false;
+        if (a.pshare[p] != (q.share < 0 ? (uint32_t)AMAX : (uint32_t)q.share)) return false;
+        if (a.pldw[p] != (q.share < 0 ? q.width : 0u)) return false;
+        if (a.pguard[p] != (q.guard < 0 ? (uint32_t)AMAX : (uint32_t)q.guard)) return false;
+    }
+    return true;
+}
+// the registered plan (its id) an update of key layout L with arguments a runs, 0: none
+template <class L>
+int plan_for_update(const GbArgs &a) {
+    if constexpr (std::is_same<L, StaticLayout<16, 16, 8, 4, 16, 2, 2, 2>>::value)
+        return plan_matches(TopTcpPlan::D, a) ? TopTcpPlan::D.id : 0;
+    else if constexpr (std::is_same<L, StaticLayout<8, 4, 4, 4>>::value)
+        return plan_matches(TopFilePlan::D, a) ? TopFilePlan::D.id : 0;
+    else
+        return 0;
 }
 
 __device__ __forceinline__ uint64_t row_gidx(const GbArgs &a, uint64_t row) {
@@ -720,6 +905,8 @@ struct igx_table {
     bool prefer_sm = false;      // the last interval missed the LDS cache on most rows
     bool more_probers = false;   // ... on more than MORE_PROBERS_ON_PM / 1000 of its rows (hysteresis below)
     uint32_t miss_pm = 0;        // LDS misses per 1000 rows of the last measured cached interval
+    bool rowplan_on = true;      // cached updates of a registered shape run its plan's instance (IGX_GB_ROWPLAN=0: never)
+    int rowplan_last = 0;        // the plan the last cached update ran (igx_groupby_rowplan; 0: the run-time shape)
     uint32_t mode = IGX_GB_AUTO; // igx_groupby_set_mode
     uint32_t direct_left = 0;    // AUTO: intervals to run in the direct form before re-measuring
     uint32_t region_off = 0;     // AUTO: intervals to partition exactly after a region overflowed

@@ -764,8 +764,9 @@ static int plan_aggs(igx_table *t, const igx_col *cols, uint32_t ncols, GbArgs &
 // Up to PMAX scalar comparisons (and IN sets) are fused into the kernel; any others --
 // more predicates, regex or string rules -- are AND-ed into a row mask first by a scan
 // with the filter's predicate evaluator (k_common.h), which then masks rows like `valid`.
+// (dry: plan only, nothing is launched -- predicates that would need the mask scan fail with IGX_ENOTSUP)
 static int plan_preds(igx_table *t, const igx_col *cols, uint32_t ncols, const igx_pred *preds, uint32_t npreds,
-                      const uint8_t *valid, uint64_t nrows, GbArgs &a) {
+                      const uint8_t *valid, uint64_t nrows, GbArgs &a, bool dry = false) {
     igx_ctx *ctx = t->ctx;
     const uint8_t *dummy = a.kcol[0];
     std::vector<igx_pred> fused, masked;
@@ -810,6 +811,7 @@ static int plan_preds(igx_table *t, const igx_col *cols, uint32_t ncols, const i
         masked.push_back(*it);
         fused.erase(it);
     }
+    if (!masked.empty() && dry) return IGX_ENOTSUP;
     if (!masked.empty()) {
         int rc = grow(ctx, reinterpret_cast<void **>(&t->p_mask), &t->p_mask_bytes, igx_align(nrows, 256));
         if (rc) return rc;
@@ -887,6 +889,8 @@ static int bind_table(igx_table *t, const igx_col *cols, uint32_t ncols, uint32_
     a.base_idx = base_idx;
     bind_records(t, a);
     if (const char *d = std::getenv("IGX_GB_DEBUG")) a.dbg = (uint32_t)std::strtoul(d, nullptr, 0);
+    t->rowplan_on = true;
+    if (const char *d = std::getenv("IGX_GB_ROWPLAN")) t->rowplan_on = std::strtoul(d, nullptr, 0) != 0;   // A/B and test knob
     // one loader wave fewer (one prober more) after intervals that missed the cache on more
     // than MORE_PROBERS_ON_PM / 1000 of their rows (until one falls below MORE_PROBERS_OFF_PM)
     a.nl = t->more_probers ? NL_DEFAULT - 1 : NL_DEFAULT;
@@ -953,6 +957,37 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
     if ((rc = launch_form(t, a))) return rc;
     IGX_HIP(ctx, hipGetLastError());
     return IGX_OK;
+}
+
+extern "C" int igx_groupby_rowplan(igx_table *t) { return t ? t->rowplan_last : 0; }
+
+// The registry's answer for an update described as igx_groupby_create and igx_groupby_update_ex
+// describe it, without a table or a device: the update is planned as usual (column pointers are
+// compared, never read) and matched as gb_launch_cached matches it.
+extern "C" int igx_groupby_rowplan_match(const uint32_t *key_widths, uint32_t nkeys, const igx_agg *aggs,
+                                         uint32_t naggs, const igx_col *cols, uint32_t ncols,
+                                         const uint32_t *key_cols, const igx_pred *preds, uint32_t npreds,
+                                         const uint8_t *valid, uint32_t idx_col) {
+    if (!key_widths || !cols || !key_cols || nkeys == 0 || nkeys > 16 || naggs > AMAX || (naggs && !aggs)) return 0;
+    igx_table t{};
+    t.nkeys = nkeys;
+    for (uint32_t k = 0; k < nkeys; ++k) {
+        t.key_widths[k] = key_widths[k];
+        t.key_words += (key_widths[k] + 3) / 4;
+    }
+    t.naggs = naggs;
+    for (uint32_t x = 0; x < naggs; ++x) t.aggs[x] = aggs[x];
+    GbArgs a{};
+    if (plan_keys(&t, cols, ncols, key_cols, a) || plan_aggs(&t, cols, ncols, a) ||
+        plan_preds(&t, cols, ncols, preds, npreds, valid, 0, a, true))
+        return 0;
+    if (idx_col != IGX_NO_COL) a.fidx = reinterpret_cast<const uint64_t *>(cols);   // present: any non-null value
+    int plan = 0;
+    (void)gb_with_layout(&t, [&](auto tag) {
+        plan = plan_for_update<typename decltype(tag)::type>(a);
+        return (int)IGX_OK;
+    });
+    return plan;
 }
 
 // finalize's device part: the occupied-slot list and the group count, then the count, the

@@ -260,6 +260,11 @@ class Table:
         self.ctx.check(self.ctx.L.igx_groupby_info(self.h, C.byref(v)))
         return {f: getattr(v, f) for f, _ in GroupbyInfo._fields_ if f != "pad"}
 
+    def rowplan(self):
+        """igx_groupby_rowplan: the row plan the last cached update ran (0 general, 1 top tcp,
+        2 top file)."""
+        return int(self.ctx.L.igx_groupby_rowplan(self.h))
+
     def reset(self):
         self.ctx.check(self.ctx.L.igx_groupby_reset(self.h))
 
