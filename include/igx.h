@@ -342,9 +342,16 @@ int igx_groupby_create(igx_ctx *ctx, const uint32_t *key_widths, uint32_t nkeys,
  * would be misaligned and would run up to three bytes past its last row); copy such a slice
  * first.  The bytes up to the next 4-byte boundary after a column's last row are read and must
  * be readable, which holds for any HIP allocation.  String predicate columns take any address.
- * base_idx is the global index of row 0 (first-occurrence order); indices must
- * stay below 2^48 - 1 (IGX_EINVAL otherwise; an index column value at or above it fails the
- * interval at finalize): long-running streams rebase their indices per interval.  Async. */
+ * base_idx is the global index of row 0 (first-occurrence order).  Event indices must stay
+ * below 2^48 - 2 on every path: the table stores an index in 48 bits next to the interval's
+ * epoch, a new key's as index + 1 and a kept key's (igx_groupby_reset's generations) as
+ * index + 2, and the one limit is the smaller of the two, so a key accepts and rejects the same
+ * values whether the interval inserts it or finds it kept.  A row index that would reach the
+ * limit (base_idx + nrows - 1 >= 2^48 - 2) returns IGX_EINVAL and nothing is issued; an index
+ * column value (igx_groupby_update_ex) at or above it fails the interval with IGX_ENOSPC at
+ * finalize -- in the cached form on any row, in the direct and partitioned forms where it would
+ * become a group's stored index -- and the next interval is unaffected.  Long-running streams
+ * rebase their indices per interval.  Async. */
 int igx_groupby_update(igx_table *t, const igx_col *cols, uint32_t ncols,
                        const uint32_t *key_cols, const igx_pred *preds, uint32_t npreds,
                        uint64_t nrows, uint64_t base_idx);
@@ -653,6 +660,11 @@ int igx_partition_rows(igx_ctx *ctx, const uint8_t *rows, uint64_t nrows, uint32
  * (nullable: 8) | first index) grouped by owner part, stable in slot order within a part.  The
  * group count is read on the device (view->d_n_groups), so an asynchronously finalized table
  * is partitioned without a host round trip; out holds cap_rows rows (>= the table's capacity).
+ * Overflow: a table may list more groups than cap_rows (an interval over its capacity whose
+ * IGX_ENOSPC has not been collected yet: finalized asynchronously and not waited on).  Then no
+ * more than cap_rows rows are written and EVERY part_counts[p] is UINT64_MAX (-1 read as int64):
+ * the rows are incomplete and no count is a send count.  Callers test the counts they read back
+ * before using them (the Python binding's dist.exchange_partitioned raises IGX_ENOSPC).
  * The sender side of the owner exchange (C4 / C5 at N > 1; replaces the reference's per-node
  * fan-out + client merge, grpc-runtime.go:221-237 -> snapshotcombiner.go:79-106).  Async. */
 int igx_partition_groups(igx_ctx *ctx, const igx_table_view *view, const uint32_t *out_widths,

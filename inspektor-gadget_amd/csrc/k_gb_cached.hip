@@ -447,7 +447,7 @@ __device__ __forceinline__ void finish_miss(const GbArgs &a, const LdsCache<KW> 
 // whichever `ready` lands, every later reader's first_ins is met.  Returns the first_ins to use.
 template <int KW>
 __device__ __forceinline__ uint64_t restamp(const GbArgs &a, uint64_t s, uint64_t gidx) {
-    if (gidx + 1 >= READY_IDX) {   // an index column value that `ready` cannot carry
+    if (gidx >= IDX_LIMIT) {   // an index column value that `ready` cannot carry
         atomicOr(a.err, 8u);
         return READY_IDX;          // still correct: every event pushes its minimum
     }
@@ -786,7 +786,7 @@ __device__ __forceinline__ void prober(const GbArgs &a, const LdsCache<KW> &c, c
                     uint64_t ready = (uint64_t)d[j][KOFF / 4 + 2] | ((uint64_t)d[j][KOFF / 4 + 3] << 32);
                     bool next = false;
                     if ((t & EP_MAX) != gep) {   // empty in this generation: claim it
-                        if (x[j].gidx >= READY_IDX) {   // an index column value that `ready` cannot carry
+                        if (x[j].gidx >= IDX_LIMIT) {   // an index column value that `ready` cannot carry
                             atomicOr(a.err, 8u);
                             act[j] = false;
                         } else {
@@ -949,6 +949,13 @@ __global__ __launch_bounds__(GTB) void k_groupby(GbArgs a) {
             const uint64_t h = hash_key<KW>(k);
             if (DBG && (a.dbg & 1u)) {   // diagnostics: load + hash only
                 if (ok && h == 0x1234567ull && v[0] == 7) atomicAdd(a.dbg_cnt + 3, 1ull);   // keep live
+                ok = false;
+            }
+            // an index column value `ready` cannot carry fails the interval here, before the cache:
+            // an LDS hit never reaches a claim's or a re-stamp's check (a seeded key may see only
+            // hits), and the state-machine probers claim without one
+            if (ok && a.fidx && row_gidx(a, row) >= IDX_LIMIT) {
+                atomicOr(a.err, 8u);
                 ok = false;
             }
             if (ok) {

@@ -78,6 +78,11 @@ constexpr int PMAX = 2;   // more predicates: run igx_filter first
 constexpr int GTB = 1024;
 constexpr uint64_t EP_MAX = 0xFFFF;              // epoch bits in a tag / in `ready`
 constexpr uint64_t READY_IDX = (1ull << 48) - 1;  // `ready` = epoch << 48 | (first_ins + 1)
+// Event indices stay below IDX_LIMIT on every path (include/igx.h, igx_groupby_update): a kept key's
+// re-stamp stores index + 2 in `ready`'s 48 bits, one more than a claim does, so the claims, the
+// re-stamp and the host's row-index guard all compare against this one constant and a fresh and a
+// kept key accept and reject the same values.
+constexpr uint64_t IDX_LIMIT = READY_IDX - 1;
 // Every wait on another wave is bounded: a wait that never ends sets err bit 4
 // (igx_groupby_finalize then fails with IGX_ENOSPC) instead of hanging the GPU.
 constexpr uint32_t SPIN_LIMIT = 1u << 24;
@@ -457,7 +462,7 @@ __device__ __forceinline__ uint32_t find_or_insert(const GbArgs &a, const uint32
         uint64_t t = (uint64_t)rec_word<WIDE>(d, KOFF / 4) | ((uint64_t)rec_word<WIDE>(d, KOFF / 4 + 1) << 32);
         uint64_t ready = (uint64_t)rec_word<WIDE>(d, KOFF / 4 + 2) | ((uint64_t)rec_word<WIDE>(d, KOFF / 4 + 3) << 32);
         if ((t & EP_MAX) != a.ep) {   // empty in this interval (never claimed, or an older epoch's)
-            if (gidx >= READY_IDX) {   // an index column value that `ready` cannot carry
+            if (gidx >= IDX_LIMIT) {   // an index column value that `ready` cannot carry
                 atomicOr(a.err, 8u);
                 return SLOT_OVF;
             }

@@ -497,6 +497,13 @@ extern "C" int igx_groupby_reset(igx_table *t) {
         IGX_HIP(ctx, hipGetLastError());
         t->ep = 1;
         wrapped = true;
+        // Seeds are identified by their generation's first epoch (*seed_gep), and epochs repeat
+        // after the wrap: a table's first generation and the one after the wrap both start at
+        // epoch 1.  The cleared table holds none of the seeds' slots, so they end here -- not when
+        // the wrapped interval's read-back is collected (fin_apply), which under asynchronous
+        // finalizes is usually after the next interval has adopted them.
+        t->nseeds = 0;
+        t->seed_left = 0;
     }
     // The generation goes on (the device checks its key count) when the last interval's groups
     // were listed by a finalize after its last update and this interval is planned in the cached
@@ -940,7 +947,9 @@ extern "C" int igx_groupby_update_ex(igx_table *t, const igx_col *cols, uint32_t
     if (nrows == 0) return IGX_OK;
     if (!cols || !key_cols) return igx_fail(ctx, IGX_EINVAL, "groupby_update: null columns");
     if (nrows >= (1ull << 32)) return igx_fail(ctx, IGX_EINVAL, "groupby_update: more than 2^32 rows in one call");
-    if (base_idx + nrows >= READY_IDX)   // `ready` carries first_ins + 1 (a kept key's: index + 2) in 48 bits
+    // `ready` carries first_ins + 1 (a kept key's: index + 2) in 48 bits: the last row's index stays
+    // below IDX_LIMIT (written so that a base_idx near 2^64 cannot wrap past the test)
+    if (base_idx >= IDX_LIMIT || nrows > IDX_LIMIT - base_idx)
         return igx_fail(ctx, IGX_EINVAL, "groupby_update: event indices reach 2^48 (rebase the interval's indices)");
     t->rows_fed += nrows;
     t->fin_since_update = false;

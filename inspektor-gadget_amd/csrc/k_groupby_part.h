@@ -739,7 +739,7 @@ __device__ __forceinline__ void flush_owned(const GbArgs &a, const AggTab<KW> &T
         atomicOr(a.err, 32u);
         return;
     }
-    if (f >= READY_IDX) {   // an index column value that `ready` cannot carry (as find_or_insert)
+    if (f >= IDX_LIMIT) {   // an index column value that `ready` cannot carry (as find_or_insert)
         atomicOr(a.err, 8u);
         return;
     }

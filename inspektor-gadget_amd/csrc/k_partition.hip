@@ -42,8 +42,11 @@ __global__ __launch_bounds__(PTB) void k_part_hist(const uint8_t *__restrict__ r
 }
 
 // exclusive scan of hist in [part][block] order (one block; nparts * nblocks <= 65536)
+// ng (nullable) / cap: igx_partition_groups' group count on the device and the rows its output
+// holds; more groups than that and every count reads UINT64_MAX (the rows were truncated)
 __global__ __launch_bounds__(PTB) void k_part_scan(uint32_t *__restrict__ v, uint32_t m, uint32_t nparts,
-                                                   uint32_t nblocks, uint64_t *__restrict__ part_counts) {
+                                                   uint32_t nblocks, uint64_t *__restrict__ part_counts,
+                                                   const uint64_t *__restrict__ ng = nullptr, uint64_t cap = 0) {
     __shared__ uint32_t part[PTB];
     const uint32_t per = (m + PTB - 1) / PTB;
     const uint32_t b = threadIdx.x * per, e = min(m, b + per);
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(PTB) void k_part_scan(uint32_t *__restrict__ v, uin
     if (threadIdx.x < nparts) {
         const uint32_t lo = v[threadIdx.x * nblocks];
         const uint32_t hi = threadIdx.x + 1 < nparts ? v[(threadIdx.x + 1) * nblocks] : part[PTB - 1];
-        part_counts[threadIdx.x] = hi - lo;
+        part_counts[threadIdx.x] = ng && *ng > cap ? ~0ull : (uint64_t)(hi - lo);
     }
 }
 
@@ -314,7 +317,7 @@ extern "C" int igx_partition_rows(igx_ctx *ctx, const uint8_t *rows, uint64_t nr
     hipLaunchKernelGGL(k_part_hist, dim3(nblocks), dim3(PTB), 0, ctx->stream, rows, nrows, row_bytes, kw, nparts,
                        chunk, hist);
     hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(PTB), 0, ctx->stream, hist, nparts * nblocks, nparts, nblocks,
-                       part_counts);
+                       part_counts, (const uint64_t *)nullptr, (uint64_t)0);
     hipLaunchKernelGGL(k_part_scatter, dim3(nblocks), dim3(PTB), 0, ctx->stream, rows, nrows, row_bytes, kw, nparts,
                        chunk, hist, out);
     IGX_HIP(ctx, hipGetLastError());
@@ -361,7 +364,7 @@ extern "C" int igx_partition_groups(igx_ctx *ctx, const igx_table_view *view, co
     uint8_t *owner = static_cast<uint8_t *>(scratch) + hist_b;   // each row's owner, from the first pass
     hipLaunchKernelGGL(k_gpart_hist, dim3(nblocks), dim3(PTB), 0, ctx->stream, g, nparts, hist, owner);
     hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(PTB), 0, ctx->stream, hist, nparts * nblocks, nparts, nblocks,
-                       part_counts);
+                       part_counts, g.ng, g.cap);
     hipLaunchKernelGGL(k_gpart_scatter, dim3(nblocks), dim3(PTB), 0, ctx->stream, g, nparts, hist, owner, out);
     IGX_HIP(ctx, hipGetLastError());
     return IGX_OK;

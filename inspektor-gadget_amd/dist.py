@@ -264,7 +264,13 @@ def partition_by_owner(rows, key_bytes, ws):
 def exchange_partitioned(rows, counts, c=None):
     """All-to-all of rows already grouped by destination rank (counts[r] rows for rank r,
     in rank order; rows past their sum are ignored).  Returns the rows this rank owns, in
-    source-rank order."""
+    source-rank order.  Negative counts are igx_partition_groups' overflow sentinel (the table
+    listed more groups than the partition's output holds, so the rows are truncated): IgxError
+    with IGX_ENOSPC, before anything is sent."""
+    if any(int(n) < 0 for n in counts):
+        from . import _abi
+        raise _abi.IgxError(_abi.IGX_ENOSPC, "exchange_partitioned: the partitioned table held more groups than "
+                                             "its capacity (igx_partition_groups' counts are -1): rows truncated")
     c = c or comm()
     rows = rows[:sum(counts)]
     return rows if c is None else c.alltoallv_rows(rows, counts)

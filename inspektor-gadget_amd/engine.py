@@ -383,7 +383,9 @@ class Table:
         mod nparts, as igx_partition_rows), stable in slot order within a part -- the sender
         side of the owner exchange, with the group count read on the device (works after
         finalize(sync=False)).  Returns (rows (capacity, row_bytes) u8, counts (nparts,) i64),
-        both on the device; rows past the counts' sum are unused."""
+        both on the device; rows past the counts' sum are unused.  A table that lists more groups
+        than its capacity (an over-capacity interval whose IGX_ENOSPC was not collected yet) gives
+        -1 in every count: the rows are truncated (dist.exchange_partitioned raises on them)."""
         torch = torch_mod()
         ctx = self.ctx
         ctx.bind_stream()

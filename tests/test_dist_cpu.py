@@ -24,3 +24,25 @@ def test_world2_gloo_merges():
            os.path.join(ROOT, "tests", "dist_worker.py")]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "DIST_OK" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
+
+
+def test_exchange_partitioned_rejects_the_overflow_sentinel():
+    """igx_partition_groups writes UINT64_MAX into every count when the table lists more groups
+    than the output holds; through the binding's int64 tensor that is -1.  exchange_partitioned
+    must refuse such counts with IGX_ENOSPC before it slices or sends anything (rows[:sum(counts)]
+    of negative counts would silently drop rows from the end), and pass sane counts through."""
+    import importlib
+
+    import pytest
+    import torch
+    D = importlib.import_module("inspektor-gadget_amd.dist")
+    A = importlib.import_module("inspektor-gadget_amd._abi")
+    rows = torch.arange(40, dtype=torch.uint8).reshape(10, 4)
+    sentinel = torch.full((4,), -1, dtype=torch.int64)
+    assert sentinel.view(torch.uint64)[0].item() == 2 ** 64 - 1
+    for counts in (sentinel.tolist(), [3, -1, 2, 1], [-1]):
+        with pytest.raises(A.IgxError) as ei:
+            D.exchange_partitioned(rows, counts)
+        assert ei.value.code == A.IGX_ENOSPC
+    assert torch.equal(D.exchange_partitioned(rows, [4, 3, 0, 2]), rows[:9])   # one rank: its own rows
+    assert D.exchange_partitioned(rows, [0, 0]).shape[0] == 0

@@ -7,6 +7,11 @@ test_partition_groups_matches_partition_rows: the table-view partition equals
 igx_partition_rows over the gathered rows, after a synchronous and an asynchronous finalize,
 for the top-file layout (4 aggregates) and the distinct-only network-policy tuple.
 
+test_partition_overflow_is_loud_and_full_table_is_exact: a table that lists more groups than the
+partition's output holds (over capacity, finalized asynchronously, never waited on) gives
+UINT64_MAX in every count, which dist.exchange_partitioned refuses; one exactly at capacity
+partitions to exactly its rows.
+
 test_emulated_rank_of_8_owner_merge: one GPU plays rank 0 of 8.  Eight slices of one global
 stream are aggregated into partial tables; each is partitioned by owner and owner 0's rows are
 kept (what the all-to-all would deliver, the transfer itself left out); rank 0 merges them into
@@ -68,6 +73,52 @@ def test_partition_groups_matches_partition_rows(igx, torch):
     assert counts == rcnt and torch.equal(prow[:G], ref)
     tab.destroy()
     tab4.destroy()
+
+
+def test_partition_overflow_is_loud_and_full_table_is_exact(igx, torch, oracle):
+    """More groups than the partition's output holds (a table over capacity but within its slots,
+    test_capacity_overflow_is_reported's: capacity 1000, 5000 keys; finalized asynchronously and
+    never waited on, as a benchmark step's last interval can be): every count is UINT64_MAX, -1
+    through the binding's int64 tensor, and dist.exchange_partitioned refuses them with
+    IGX_ENOSPC -- where igx_partition_groups used to hand back 1000 of the groups and counts that
+    summed to 1000.  A table exactly at capacity partitions to exactly its gathered rows."""
+    E, H, A, D = igx.engine, igx.columns, igx._abi, igx.dist
+    bench = importlib.import_module("bench")
+    G, n = 5000, 200_000
+    ev_h = oracle.gen_tcp(0xC2, 0, G, oracle.zipf_cdf(G, 0.5), 0, n)
+    pid = H.to_device(ev_h["pid"])
+    distinct = int(np.unique(ev_h["pid"]).size)
+    assert distinct > 1000
+    tab = E.Table([4], [A.Agg(A.AGG_COUNT, 0, A.NO_COL, 8, 0)], 1000)
+    tab.update([pid], [0], n, 0)
+    tab.finalize(sync=False)
+    prow, cnt = tab.partition(8)
+    counts = cnt.cpu().tolist()
+    assert counts == [-1] * 8, counts
+    assert cnt.view(torch.uint64).cpu()[0].item() == 2 ** 64 - 1
+    with pytest.raises(A.IgxError) as ei:
+        D.exchange_partitioned(prow, counts)
+    assert ei.value.code == A.IGX_ENOSPC
+    with pytest.raises(A.IgxError) as ei:              # the interval's own status, still reported
+        tab.wait()
+    assert ei.value.code == A.IGX_ENOSPC
+    tab.destroy()
+    # exactly at capacity: nothing is cut and nothing is flagged
+    full = E.Table([4], [A.Agg(A.AGG_COUNT, 0, A.NO_COL, 8, 0)], distinct)
+    full.update([pid], [0], n, 0)
+    full.finalize(sync=False)
+    prow, cnt = full.partition(8)
+    counts = cnt.cpu().tolist()
+    assert min(counts) >= 0 and sum(counts) == distinct
+    assert full.wait() == distinct
+    ref, rcnt = E.partition_rows(bench.table_rows(E, torch, full, full.fin), full.fin["key_bytes"], 8)
+    assert counts == rcnt and torch.equal(prow[:distinct], ref)
+    # and the rows are the oracle's groups
+    k, aggs, first = oracle.groupby(oracle.pack_cols(ev_h, ("pid",)), [{"kind": "count"}])
+    want = np.concatenate([k, aggs[0].copy().view(np.uint8).reshape(-1, 8),
+                           first.copy().view(np.uint8).reshape(-1, 8)], axis=1)
+    assert np.array_equal(_rows_sorted(H.host(prow[:distinct])), _rows_sorted(want))
+    full.destroy()
 
 
 def test_emulated_rank_of_8_owner_merge(igx, torch, oracle):
