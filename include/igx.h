@@ -627,6 +627,64 @@ int igx_intern_hash_rows(const void *rows, uint32_t row_bytes, uint64_t row_stri
 int igx_ksym_lookup(igx_ctx *ctx, const uint64_t *sym_addr, uint64_t nsyms,
                     const uint64_t *ips, uint64_t n, uint32_t *out_idx);
 
+/* ---- advise seccomp-profile: per-mntns syscall sets ---------------------------------------- */
+/* ig_seccomp_e (pkg/gadgets/advise/seccomp/tracer/bpf/seccomp.bpf.c:67-139) keeps, per mount
+ * namespace, a value of 501 bytes: 500 presence bytes (one per syscall id) and a footer byte that
+ * says whether runc's rows are being recorded yet.  igx_seccomp is that map.  Per row, over the
+ * device columns mntns (u64), id (u32), arg0 (u64, PT_REGS_PARM1), comm (at comm + i *
+ * comm_stride; only its first four bytes are read) and compat (u8, nullable = all 0):
+ *   1. compat != 0, id >= 500 or mntns == 0: the row is dropped and makes no entry.
+ *   2. otherwise the entry of mntns exists from this row on, even if nothing is recorded in it.
+ *   3. a row whose comm starts with "runc", while the entry is not armed: if id == nr_prctl and
+ *      arg0 == 2 (PR_GET_PDEATHSIG; all 64 bits compared) it arms the entry; it records nothing.
+ *   4. such a row when the entry is armed: (id == nr_prctl and arg0 == 38, PR_SET_NO_NEW_PRIVS) or
+ *      id == nr_seccomp records nothing; every other row records, a later prctl(2) included.
+ *   5. any other row records: value[id] = 1.
+ * Rows with valid[i] == 0 (valid nullable) are skipped.  The object counts the rows of all updates,
+ * so the result is a function of the stream alone, however it is cut into updates.  nr_prctl and
+ * nr_seccomp are fixed at creation (157 / 317 on x86_64, 167 / 277 on arm64).
+ *
+ * igx_seccomp_peek (asynchronous): for n namespaces at mntns (device), out (device, n x 501
+ * bytes) receives the values and found (device, n bytes) whether the entry exists; an absent
+ * entry's value is zero.  Namespace 0 is found and blank: the reference installs a blank value at
+ * key 0 (tracer.go:77).  igx_seccomp_delete (asynchronous) removes the entries of n namespaces
+ * (device; absent ones are ignored): a later row of that namespace starts from a blank, unarmed
+ * value.  igx_seccomp_list (synchronises): *n = the number of entries, the first min(*n, cap) of
+ * them written to out (device u64) in no particular order.  igx_seccomp_count (synchronises): the
+ * number of entries.
+ *
+ * Capacity is the number of distinct namespaces the object can ever hold: a deleted namespace
+ * keeps its slot (so that the probe chains of others stay whole, and its own rows find it again)
+ * and keeps counting against capacity.  The table has S slots, S the smallest power of two that
+ * is at least 2 x capacity and at least 2 (igx_seccomp_slots); tables of up to 2048 slots are
+ * marked through LDS, larger ones in global memory, with the same result.  When an update takes
+ * the distinct namespaces past capacity, the values are unspecified from then on (nothing is
+ * written out of bounds), igx_seccomp_count and igx_seccomp_list return IGX_ENOSPC, and once one
+ * of them has, igx_seccomp_update does too.  The reference's max_entries of 1024 and its silent
+ * drop of new namespaces in a full map are kernel artifacts and are not reproduced.
+ *
+ * Limits (IGX_EINVAL otherwise, checked before any GPU work): capacity in 1..2^19; comm_stride >=
+ * 4; no null column when nrows > 0 (compat and valid may be null); mntns and arg0 8-byte, id
+ * 4-byte aligned; nrows <= 2^31 - 1 (0 is valid).  Memory: 81 bytes per slot and per-call scratch
+ * of 4 bytes per row; device memory that cannot be had returns IGX_ENOMEM and nothing stays
+ * allocated.
+ *
+ * igx_seccomp_home (host only, no GPU): *home = the slot a namespace's probe starts at in a table
+ * of nslots (a power of two; IGX_EINVAL otherwise); probing is linear from there.  With it a
+ * caller can build namespaces that share a home slot, the table's worst case. */
+typedef struct igx_seccomp igx_seccomp;
+int igx_seccomp_create(igx_ctx *ctx, uint64_t capacity, uint32_t nr_prctl, uint32_t nr_seccomp, igx_seccomp **out);
+int igx_seccomp_update(igx_seccomp *t, const uint64_t *mntns, const uint32_t *id, const uint64_t *arg0,
+                       const void *comm, uint64_t comm_stride, const uint8_t *compat /*nullable*/,
+                       const uint8_t *valid /*nullable*/, uint64_t nrows);
+int igx_seccomp_peek(igx_seccomp *t, const uint64_t *mntns, uint64_t n, uint8_t *out, uint8_t *found);
+int igx_seccomp_delete(igx_seccomp *t, const uint64_t *mntns, uint64_t n);
+int igx_seccomp_list(igx_seccomp *t, uint64_t *out, uint64_t cap, uint64_t *n);
+int igx_seccomp_count(igx_seccomp *t, uint64_t *n);
+int igx_seccomp_slots(igx_seccomp *t, uint64_t *n_slots);
+int igx_seccomp_destroy(igx_seccomp *t);
+int igx_seccomp_home(uint64_t mntns, uint64_t nslots, uint64_t *home);
+
 /* ---- group:sum of float columns, IP text --------------------------------------------- */
 /* GroupEntries' float group:sum (group.go:133-156, flattenValues): perm (device u32, n) is a
  * stable sort of the rows by the group key (key_bytes at row * key_stride of keys); each run

@@ -31,6 +31,7 @@ AGG_COUNT, AGG_SUM = 0, 1
 FILTER_ANY, FILTER_NIL_MATCH = 1, 2
 GB_AUTO, GB_CACHED, GB_DIRECT, GB_PART = 0, 1, 2, 3
 REQ_START, REQ_ISSUE, REQ_DONE = 0, 1, 2
+SECCOMP_SYSCALLS, SECCOMP_VALUE_BYTES = 500, 501
 
 
 class SchemaCol(C.Structure):
@@ -174,6 +175,15 @@ SIGNATURES = [
     ("igx_intern_destroy", _I, [_VP]),
     ("igx_intern_hash_rows", _I, [_VP, _U32, _U64, _U64, _VP]),
     ("igx_ksym_lookup", _I, [_VP, _VP, _U64, _VP, _U64, _VP]),
+    ("igx_seccomp_create", _I, [_VP, _U64, _U32, _U32, C.POINTER(_VP)]),
+    ("igx_seccomp_update", _I, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _VP, _U64]),
+    ("igx_seccomp_peek", _I, [_VP, _VP, _U64, _VP, _VP]),
+    ("igx_seccomp_delete", _I, [_VP, _VP, _U64]),
+    ("igx_seccomp_list", _I, [_VP, _VP, _U64, C.POINTER(_U64)]),
+    ("igx_seccomp_count", _I, [_VP, C.POINTER(_U64)]),
+    ("igx_seccomp_slots", _I, [_VP, C.POINTER(_U64)]),
+    ("igx_seccomp_destroy", _I, [_VP]),
+    ("igx_seccomp_home", _I, [_U64, _U64, C.POINTER(_U64)]),
     ("igx_partition_rows", _I, [_VP, _VP, _U64, _U32, _U32, _U32, _VP, _VP]),
     ("igx_partition_groups", _I, [_VP, _VP, _VP, _U32, _VP, _U64, _VP]),
     ("igx_dist_get_unique_id", _I, [_VP]),

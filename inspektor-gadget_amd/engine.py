@@ -661,6 +661,107 @@ def ksym_lookup(sym_addr, ips):
 
 
 # ------------------------------------------------------------------------------------
+# advise seccomp-profile: per-mntns syscall sets
+# ------------------------------------------------------------------------------------
+class SeccompMap:
+    """igx_seccomp: the syscalls_per_mntns map of advise seccomp-profile (the contract is in
+    include/igx.h).  Columns are device tensors; namespaces for peek / delete are host ints."""
+
+    def __init__(self, capacity=1024, nr_prctl=157, nr_seccomp=317, ctx=None):
+        self.ctx = context() if ctx is None else ctx
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.L.igx_seccomp_create(self.ctx.h, capacity, nr_prctl, nr_seccomp, C.byref(h)))
+        self.h = h
+        self.capacity = capacity
+
+    def update(self, mntns, id, arg0, comm, compat=None, valid=None):
+        """igx_seccomp_update (asynchronous).  mntns, arg0: 8-byte, id: 4-byte, compat, valid: 1-byte
+        integer tensors of n rows; comm: (n, w) uint8 with w >= 4 (a row stride larger than w is
+        passed through)."""
+        self.ctx.bind_stream()
+        n = int(mntns.numel())
+        if comm.dim() != 2 or comm.element_size() != 1 or comm.shape[0] != n:
+            raise ValueError("comm must be (n, width) bytes")
+        if n > 1 and comm.stride(1) != 1:
+            comm = comm.contiguous()
+        stride = comm.stride(0) if n > 1 else comm.shape[1]
+        cols = [mntns, id, arg0, compat, valid]
+        for t, size in zip(cols, (8, 4, 8, 1, 1)):
+            if t is not None and (t.element_size() != size or t.numel() != n):
+                raise ValueError("column of the wrong width or length")
+        mntns, id, arg0, compat, valid = (None if t is None else t.contiguous() for t in cols)
+        self.ctx.check(self.ctx.L.igx_seccomp_update(self.h, ptr(mntns), ptr(id), ptr(arg0), ptr(comm), stride,
+                                                     ptr(compat), ptr(valid), n))
+
+    def _keys(self, mntns):
+        import numpy as np
+        torch = torch_mod()
+        a = np.ascontiguousarray(np.asarray(mntns, dtype=np.uint64).reshape(-1))
+        return torch.from_numpy(a.view(np.int64)).to(f"cuda:{self.ctx.device}"), a.size
+
+    def peek(self, mntns):
+        """igx_seccomp_peek: (values, found) as numpy uint8 arrays of (n, 501) and (n,)."""
+        torch = torch_mod()
+        self.ctx.bind_stream()
+        keys, n = self._keys(mntns)
+        out = torch.empty((max(1, n), _abi.SECCOMP_VALUE_BYTES), dtype=torch.uint8, device=keys.device)
+        found = torch.empty(max(1, n), dtype=torch.uint8, device=keys.device)
+        self.ctx.check(self.ctx.L.igx_seccomp_peek(self.h, ptr(keys), n, ptr(out), ptr(found)))
+        return out[:n].cpu().numpy(), found[:n].cpu().numpy()
+
+    def delete(self, mntns):
+        """igx_seccomp_delete (asynchronous)."""
+        self.ctx.bind_stream()
+        keys, n = self._keys(mntns)
+        self.ctx.check(self.ctx.L.igx_seccomp_delete(self.h, ptr(keys), n))
+
+    def list(self):
+        """igx_seccomp_list (synchronises): the namespaces that have an entry, sorted."""
+        import numpy as np
+        torch = torch_mod()
+        self.ctx.bind_stream()
+        cap = 2 * self.capacity   # no more than S slots can be live
+        out = torch.empty(cap, dtype=torch.int64, device=f"cuda:{self.ctx.device}")
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.L.igx_seccomp_list(self.h, ptr(out), cap, C.byref(n)))
+        return np.sort(out[:n.value].cpu().numpy().view(np.uint64))
+
+    def count(self):
+        """igx_seccomp_count (synchronises): entries; IgxError(IGX_ENOSPC) once the capacity has
+        overflowed."""
+        self.ctx.bind_stream()
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.L.igx_seccomp_count(self.h, C.byref(n)))
+        return n.value
+
+    def slots(self):
+        """igx_seccomp_slots (host): S."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.L.igx_seccomp_slots(self.h, C.byref(n)))
+        return n.value
+
+    def destroy(self):
+        if self.h:
+            self.ctx.L.igx_seccomp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def seccomp_home(mntns, nslots):
+    """igx_seccomp_home (host, no GPU): the slot a namespace's probe starts at among nslots."""
+    h = C.c_uint64()
+    rc = _abi.lib().igx_seccomp_home(mntns, nslots, C.byref(h))
+    if rc:
+        raise IgxError(rc, "igx_seccomp_home: nslots must be a power of two")
+    return h.value
+
+
+# ------------------------------------------------------------------------------------
 # data movement either side of the path
 # ------------------------------------------------------------------------------------
 def partition_rows(rows, key_bytes, nparts):

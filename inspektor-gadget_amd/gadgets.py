@@ -1051,3 +1051,180 @@ class ProfileCpuTracer:
     def destroy(self):
         self.table.destroy()
         self.stacks.destroy()
+
+
+# ------------------------------------------------------------------------------------
+# advise seccomp-profile (pkg/gadgets/advise/seccomp/tracer/tracer.go, syscalls.go;
+# pkg/gadget-collection/gadgets/advise/seccomp/syscalls.go, gadget.go:217-251)
+# ------------------------------------------------------------------------------------
+SYSCALLS_COUNT = _abi.SECCOMP_SYSCALLS
+# (__NR_prctl, __NR_seccomp) per GOARCH (seccomp.bpf.c:20-51)
+SECCOMP_NR = {"amd64": (157, 317), "arm64": (167, 277)}
+_ARCHES = {   # tracer/syscalls.go:29-48
+    "amd64": ["SCMP_ARCH_X86_64", "SCMP_ARCH_X86", "SCMP_ARCH_X32"],
+    "arm64": ["SCMP_ARCH_ARM", "SCMP_ARCH_AARCH64"],
+    "mips64": ["SCMP_ARCH_MIPS", "SCMP_ARCH_MIPS64", "SCMP_ARCH_MIPS64N32"],
+    "mips64n32": ["SCMP_ARCH_MIPS", "SCMP_ARCH_MIPS64", "SCMP_ARCH_MIPS64N32"],
+    "mipsel64": ["SCMP_ARCH_MIPSEL", "SCMP_ARCH_MIPSEL64", "SCMP_ARCH_MIPSEL64N32"],
+    "mipsel64n32": ["SCMP_ARCH_MIPSEL", "SCMP_ARCH_MIPSEL64", "SCMP_ARCH_MIPSEL64N32"],
+    "s390x": ["SCMP_ARCH_S390", "SCMP_ARCH_S390X"],
+}
+
+
+def go_marshal(v, indent: Optional[str] = None, sort_maps: bool = True, _depth: int = 0) -> str:
+    """json.Marshal (indent None) or json.MarshalIndent(v, "", indent) of nested dicts, lists,
+    strings, ints, bools and None.  A dict stands for a Go map when sort_maps (keys sorted as
+    encoding/json sorts them) and for a struct otherwise (insertion order = field order)."""
+    from . import textcolumns as T
+    if isinstance(v, dict):
+        items = sorted(v.items()) if sort_maps else list(v.items())
+        parts = [T.go_json_string(k) + (":" if indent is None else ": ") + go_marshal(x, indent, sort_maps, _depth + 1)
+                 for k, x in items]
+        o, c = "{", "}"
+    elif isinstance(v, (list, tuple)):
+        parts = [go_marshal(x, indent, sort_maps, _depth + 1) for x in v]
+        o, c = "[", "]"
+    else:
+        return T.go_json_value(v)
+    if not parts:
+        return o + c
+    if indent is None:
+        return o + ",".join(parts) + c
+    pad = "\n" + indent * (_depth + 1)
+    return o + pad + ("," + pad).join(parts) + "\n" + indent * _depth + c
+
+
+def syscallArrToNameList(value, names=None) -> List[str]:
+    """tracer.go:90-105: the names of the ids whose presence byte is set, sorted as sort.Strings
+    sorts; "syscall%d" for an id the table does not name.  names: {id: name}, default the
+    generated x86_64 table."""
+    if names is None:
+        from ._syscalls import X86_64 as names
+    out = [names.get(i) or "syscall%d" % i for i, b in enumerate(bytes(value)[:SYSCALLS_COUNT]) if b]
+    return sorted(out, key=lambda s: s.encode("utf-8", "surrogatepass"))
+
+
+def Arches(goarch: str = "amd64") -> List[str]:
+    """tracer/syscalls.go:29-48 for runtime.GOARCH == goarch."""
+    return list(_ARCHES.get(goarch, []))
+
+
+def SyscallNamesToLinuxSeccomp(syscallNames, goarch: str = "amd64") -> dict:
+    """tracer/syscalls.go:50-65 as json.Marshal lays out specs.LinuxSeccomp (field order kept):
+    the omitempty fields that are empty here -- args, flags, listener*, errno returns, and
+    architectures on an unknown GOARCH -- are left out.  names: null for None, as a nil slice."""
+    d = {"defaultAction": "SCMP_ACT_ERRNO"}
+    if Arches(goarch):
+        d["architectures"] = Arches(goarch)
+    d["syscalls"] = [{"names": None if syscallNames is None else list(syscallNames), "action": "SCMP_ACT_ALLOW"}]
+    return d
+
+
+@dataclass
+class SeccompProfileNsName:
+    """gadget.go:206-215."""
+    namespace: str = ""
+    name: str = ""
+    generateName: bool = False
+
+
+def syscallNamesToSeccompPolicy(profileName: SeccompProfileNsName, syscallNames, goarch: str = "amd64") -> dict:
+    """gadget-collection/gadgets/advise/seccomp/syscalls.go:27-62 as json.Marshal lays out the
+    security-profiles-operator's SeccompProfile: empty omitempty fields are left out (the empty
+    label and annotation maps too); creationTimestamp (a struct) and status stay."""
+    meta = {}
+    if profileName.generateName:
+        meta["generateName"] = profileName.name + "-"
+    elif profileName.name:
+        meta["name"] = profileName.name
+    if profileName.namespace:
+        meta["namespace"] = profileName.namespace
+    meta["creationTimestamp"] = None
+    spec = {"defaultAction": "SCMP_ACT_ERRNO"}
+    if Arches(goarch):
+        spec["architectures"] = Arches(goarch)
+    spec["syscalls"] = [{"names": None if syscallNames is None else list(syscallNames), "action": "SCMP_ACT_ALLOW"}]
+    return {"metadata": meta, "spec": spec, "status": {}}
+
+
+def _atoi(s: str):
+    """strconv.Atoi: an optional sign and decimal digits within int64, else None."""
+    body = s[1:] if s[:1] in ("+", "-") else s
+    if not body or not all("0" <= ch <= "9" for ch in body):
+        return None
+    v = int(s)
+    return v if -(1 << 63) <= v < (1 << 63) else None
+
+
+def getSeccompProfileNextName(profileNames, podName: str) -> str:
+    """gadget.go:217-251 over the names of the profile list.  strings.TrimLeft takes a cutset,
+    not a prefix, and so does this."""
+    counter = 0
+    for name in profileNames:
+        if not name.startswith(podName):
+            continue
+        if name == podName and counter == 0:
+            counter += 1
+            continue
+        c = _atoi(name.lstrip(podName + "-"))
+        if c is None:
+            continue
+        if c > counter:
+            counter = c
+    return podName if counter == 0 else "%s-%d" % (podName, counter + 1)
+
+
+@dataclass(eq=False)
+class SeccompContainer:
+    """What the tracer reads of a containercollection.Container.  Compared by identity, as
+    the reference's map is keyed by pointer."""
+    Name: str
+    Mntns: int
+
+
+class AdviseSeccompTracer:
+    """advise seccomp-profile: ig_seccomp_e (seccomp.bpf.c:67-139) over batches of sys_enter
+    rows, and the Tracer of tracer.go:42-179.  The map is an engine.SeccompMap; capacity bounds
+    the distinct mount namespaces it can ever hold (IgxError(IGX_ENOSPC) from Peek past it; the
+    reference's max_entries is not modelled).  names: {id: name} for syscallArrToNameList."""
+
+    def __init__(self, capacity=1024, goarch="amd64", names=None, ctx=None):
+        nr_prctl, nr_seccomp = SECCOMP_NR[goarch]
+        self.map = engine.SeccompMap(capacity, nr_prctl, nr_seccomp, ctx=ctx)
+        self.names = names
+        self.containers: Dict[object, Optional[List[str]]] = {}
+
+    def feed(self, mntns, id, arg0, comm, compat=None):
+        """One batch of sys_enter rows as device columns: mntns, arg0 u64; id u32; comm (n, 16)
+        uint8; compat u8 (is_x86_compat; None where the architecture has none)."""
+        self.map.update(mntns, id, arg0, comm, compat)
+
+    def Peek(self, mntns: int) -> List[str]:
+        """tracer.go:107-122; LookupError("no syscall found") for an absent entry."""
+        value, found = self.map.peek([mntns])
+        self.map.count()          # IGX_ENOSPC if the map overflowed
+        if not found[0]:
+            raise LookupError("no syscall found")   # the container just hasn't done any syscall
+        return syscallArrToNameList(value[0], self.names)
+
+    def Delete(self, mntns: int):
+        self.map.delete([mntns])
+
+    def AttachContainer(self, container):
+        self.containers[container] = None
+
+    def DetachContainer(self, container):
+        """tracer.go:163-171: the Peek result, or the error's text as a one-element list."""
+        try:
+            self.containers[container] = self.Peek(container.Mntns)
+        except LookupError as e:
+            self.containers[container] = [str(e)]
+
+    def collectResult(self) -> str:
+        """tracer.go:173-179: json.MarshalIndent(map[name][]string, "", "  "); a container that was
+        never detached marshals as null.  Containers that share a name keep one entry, as in
+        the reference, here the last attached."""
+        return go_marshal({c.Name: r for c, r in self.containers.items()}, indent="  ")
+
+    def destroy(self):
+        self.map.destroy()
