@@ -627,6 +627,69 @@ int igx_intern_hash_rows(const void *rows, uint32_t row_bytes, uint64_t row_stri
 int igx_ksym_lookup(igx_ctx *ctx, const uint64_t *sym_addr, uint64_t nsyms,
                     const uint64_t *ips, uint64_t n, uint32_t *out_idx);
 
+/* ---- traceloop: the enter / exit / cont join by timestamp ---------------------------------- */
+/* Tracer.Read of traceloop (pkg/gadgets/traceloop/tracer/tracer.go:246-545) joins sys_enter
+ * records, sys_exit records and "continued" parameter records by the monotonic timestamp the BPF
+ * program stamps on all of them (traceloop.bpf.c:174, :400, :410), then sorts by event time.
+ * igx_traceloop_join is that join over two record streams in the order readOverWritable's callback
+ * delivers them (reading the overwritable perf ring stays with the caller).
+ *
+ * Syscall rows (ns, device columns): mntns (u64, the container's; NULL: one container), mono_ts
+ * (u64), sort_ts (u64: the boot timestamp, or the monotonic one where the kernel has no
+ * bpf_ktime_get_boot_ns, :232-244), typ (u8: 0 enter, 1 exit), id (u16), pid (u32), valid (u8,
+ * nullable).  Cont rows (nc): c_mntns (NULL iff mntns is), c_mono_ts, c_index (u8), c_valid.
+ * Rows with valid == 0 and syscall rows of any other typ (:304-311) do not exist for the join.
+ * Only the order inside each stream matters.
+ *
+ * A group is all rows with the same (mntns, mono_ts); the reference has one map set per
+ * container.  In a group, in row order, E are the enters, X the exits, C the conts;
+ *   skip(e)   e.id is nr_exit, nr_exit_group or nr_rt_sigreturn (60 / 231 / 15 on x86_64,
+ *             93 / 94 / 139 on arm64; traceloop.bpf.c:12-35, tracer.go:418)
+ *   match(e)  the first x in X with x.id == e.id && x.pid == e.pid (:438-441)
+ *   m         the first e in E with !skip(e) and a match;   e0: the first row of E.
+ * What the loops at :362-530 publish for a group:
+ *   1. complete events: every skip enter, with no exit row; m, with exit row match(m).  Once m
+ *      matched the exit list is gone (:446) and later non-skip enters are dropped (:431-436);
+ *      non-skip enters without a match are dropped too once anything completed (:419, :445).
+ *   2. conts belong to e0 only (:415 deletes them after the first enter, whatever becomes of
+ *      it): for i in 0..5 the first row of C with index == i (:400-407).  Conts of index >= 6,
+ *      of a group without enters, or of a group whose e0 is not a complete event are lost.
+ *   3. if nothing completed, every row of E is an incomplete enter (:468-498).
+ *   4. if m does not exist, every row of X is an incomplete exit (:500-530), also when skip
+ *      enters completed.
+ * Events come out ascending by sort_ts of their own row (the enter row; the exit row for an
+ * incomplete exit).  The reference's order among equal times is map iteration followed by an
+ * unstable sort, i.e. undefined; here ties go ascending by syscall row index -- a choice within
+ * the reference's freedom.
+ *
+ * Outputs (device; ns entries each, ev_cont 6 x ns), event j in output order: ev_row[j] its
+ * syscall row; ev_class[j] 0 complete, 1 incomplete enter, 2 incomplete exit; ev_exit[j] the exit
+ * row or IGX_NO_COL; ev_cont[6 * j + i] the cont row of parameter i or IGX_NO_COL.  *d_nev (device
+ * u64) is the number of events; entries at and past it hold IGX_NO_COL (ev_class: 0xFF).
+ *
+ * Not reproduced: the maps' max_entries; WallTimeFromBootTime(0) = the wall clock now (a zero
+ * timestamp is converted like any other); the one-byte-short copy of a sample that wraps the
+ * ring (perf_buffer.go:183), which belongs to the ring reader.
+ *
+ * ns + nc <= 2^32 - 2 (0 is valid).  The u64 columns and d_nev are 8-byte aligned, pid and the
+ * row outputs 4-byte aligned, id 2-byte aligned; the outputs may not overlap the inputs or each
+ * other.  IGX_EINVAL otherwise, before any GPU work.  Work per row does not depend on the size
+ * of a group or of an (id, pid) run inside it.  Device memory of about 60 bytes per row of either
+ * stream beside the sorts' comes from the context's arenas; IGX_ENOMEM if it cannot be had, with
+ * nothing of the call's left allocated.  Two sorts, each with one host synchronisation (its digit
+ * plan); the count stays on the device.  The result is a function of the input alone.
+ * igx_traceloop_tile: the positions per tile of the device scan. */
+int igx_traceloop_join(igx_ctx *ctx,
+                       const uint64_t *mntns /*nullable*/, const uint64_t *mono_ts, const uint64_t *sort_ts,
+                       const uint8_t *typ, const uint16_t *id, const uint32_t *pid,
+                       const uint8_t *valid /*nullable*/, uint64_t ns,
+                       const uint64_t *c_mntns /*null iff mntns is*/, const uint64_t *c_mono_ts,
+                       const uint8_t *c_index, const uint8_t *c_valid /*nullable*/, uint64_t nc,
+                       uint16_t nr_exit, uint16_t nr_exit_group, uint16_t nr_rt_sigreturn,
+                       uint32_t *ev_row, uint32_t *ev_exit, uint8_t *ev_class, uint32_t *ev_cont,
+                       uint64_t *d_nev);
+int igx_traceloop_tile(void);
+
 /* ---- advise seccomp-profile: per-mntns syscall sets ---------------------------------------- */
 /* ig_seccomp_e (pkg/gadgets/advise/seccomp/tracer/bpf/seccomp.bpf.c:67-139) keeps, per mount
  * namespace, a value of 501 bytes: 500 presence bytes (one per syscall id) and a footer byte that

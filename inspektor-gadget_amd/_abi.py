@@ -184,6 +184,8 @@ SIGNATURES = [
     ("igx_seccomp_slots", _I, [_VP, C.POINTER(_U64)]),
     ("igx_seccomp_destroy", _I, [_VP]),
     ("igx_seccomp_home", _I, [_U64, _U64, C.POINTER(_U64)]),
+    ("igx_traceloop_join", _I, [_VP] * 8 + [_U64] + [_VP] * 4 + [_U64] + [C.c_uint16] * 3 + [_VP] * 5),
+    ("igx_traceloop_tile", _I, []),
     ("igx_partition_rows", _I, [_VP, _VP, _U64, _U32, _U32, _U32, _VP, _VP]),
     ("igx_partition_groups", _I, [_VP, _VP, _VP, _U32, _VP, _U64, _VP]),
     ("igx_dist_get_unique_id", _I, [_VP]),

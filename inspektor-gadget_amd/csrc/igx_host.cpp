@@ -98,6 +98,7 @@ extern "C" int igx_close(igx_ctx *ctx) {
     if (!ctx) return IGX_OK;
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
+    if (ctx->side) (void)hipFree(ctx->side);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     for (auto &r : ctx->regex) (void)hipFree(r.second);
     if (ctx->handoff) (void)hipEventDestroy(ctx->handoff);

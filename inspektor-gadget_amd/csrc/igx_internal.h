@@ -20,6 +20,9 @@ struct igx_ctx {
     // grow-only scratch arena (kernels never hipMalloc inside a call once warmed up)
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
+    // grow-only side arena: what a call keeps across a sort, which owns `scratch` while it runs
+    void *side = nullptr;
+    size_t side_bytes = 0;
     // pinned host staging for small readbacks
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -50,6 +53,8 @@ int igx_fail(igx_ctx *ctx, int code, const char *fmt, ...);
 // carved by the caller).  May synchronise the stream when it has to grow.
 int igx_scratch(igx_ctx *ctx, size_t bytes, void **out);
 int igx_pinned(igx_ctx *ctx, size_t bytes, void **out);
+// the side arena (k_traceloop.hip); may synchronise the stream when it has to grow
+int igx_side(igx_ctx *ctx, size_t bytes, void **out);
 
 static inline size_t igx_align(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

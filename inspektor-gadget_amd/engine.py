@@ -554,6 +554,57 @@ def req_join(req, kind, ts, valid=None, pend_cap=None, sync=True):
 
 
 # ------------------------------------------------------------------------------------
+# traceloop: the enter / exit / cont join by timestamp
+# ------------------------------------------------------------------------------------
+TRACELOOP_NR_X86_64 = (60, 231, 15)    # exit, exit_group, rt_sigreturn (traceloop.bpf.c:12-35)
+TRACELOOP_NR_ARM64 = (93, 94, 139)
+
+
+def traceloop_tile():
+    """igx_traceloop_tile: positions per tile of the join's device scan (host call, no GPU)."""
+    return int(_abi.lib().igx_traceloop_tile())
+
+
+def traceloop_join(mono_ts, sort_ts, typ, id, pid, valid=None, mntns=None, c_mono_ts=None, c_index=None,
+                   c_valid=None, c_mntns=None, nr=TRACELOOP_NR_X86_64, sync=True):
+    """igx_traceloop_join: traceloop's join of sys_enter, sys_exit and cont records by monotonic
+    timestamp (tracer.go:246-545; the contract is in include/igx.h).  Syscall rows: mono_ts,
+    sort_ts (u64 or int64), typ (uint8), id (uint16 or int16), pid (uint32 or int32), valid (uint8)
+    and mntns (None: one container); cont rows: c_mono_ts, c_index (uint8), c_valid, c_mntns (given
+    iff mntns is).  nr: the numbers of exit, exit_group and rt_sigreturn.
+    Returns a dict: row, exit (int32 syscall rows; exit is -1, i.e. IGX_NO_COL, without an exit
+    row), cls (uint8: 0 complete, 1 incomplete enter, 2 incomplete exit), cont ((n, 6) int32 cont
+    rows, -1 for none), one entry per event in output order, and n_events.  sync=True reads the
+    count (one host read) and trims the tensors; sync=False returns full-capacity tensors and
+    the count as a device u64 tensor."""
+    torch = torch_mod()
+    ctx = context()
+    ns = int(mono_ts.numel())
+    nc = 0 if c_mono_ts is None else int(c_mono_ts.numel())
+    dev = mono_ts.device
+    cont = lambda t: None if t is None else t.contiguous()   # noqa: E731
+    mono_ts, sort_ts, typ, id, pid, valid, mntns = (cont(t) for t in (mono_ts, sort_ts, typ, id, pid, valid, mntns))
+    c_mono_ts, c_index, c_valid, c_mntns = (cont(t) for t in (c_mono_ts, c_index, c_valid, c_mntns))
+    m = max(1, ns)
+    row, ex = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(2))
+    cls = torch.empty(m, dtype=torch.uint8, device=dev)
+    ev_cont = torch.empty((m, 6), dtype=torch.int32, device=dev)
+    cnt = torch.empty(1, dtype=torch.uint64, device=dev)
+    ctx.check(ctx.L.igx_traceloop_join(ctx.h, ptr(mntns), ptr(mono_ts), ptr(sort_ts), ptr(typ), ptr(id), ptr(pid),
+                                       ptr(valid), ns, ptr(c_mntns), ptr(c_mono_ts), ptr(c_index), ptr(c_valid), nc,
+                                       int(nr[0]), int(nr[1]), int(nr[2]), ptr(row), ptr(ex), ptr(cls), ptr(ev_cont),
+                                       C.c_void_p(cnt.data_ptr())))
+    out = {"row": row[:ns], "exit": ex[:ns], "cls": cls[:ns], "cont": ev_cont[:ns], "n_events": cnt}
+    if not sync:
+        return out
+    nev = int(cnt.cpu().view(torch.int64)[0])
+    for k in ("row", "exit", "cls", "cont"):
+        out[k] = out[k][:nev]
+    out["n_events"] = nev
+    return out
+
+
+# ------------------------------------------------------------------------------------
 # profile cpu: row interning, kernel symbol lookup
 # ------------------------------------------------------------------------------------
 def _row_view(rows, row_bytes):

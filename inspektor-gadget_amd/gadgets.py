@@ -1,5 +1,5 @@
-"""The aggregation gadgets as their tracers expose them: top tcp / file / block-io and
-profile block-io / cpu, on top of libigx.so.
+"""The aggregation gadgets as their tracers expose them: top tcp / file / block-io,
+profile block-io / cpu, advise seccomp-profile and traceloop, on top of libigx.so.
 
 Each `Top*` class is the user-space half of a reference tracer plus the BPF map update it
 drains, re-cut for batches of events resident in HBM:
@@ -1228,3 +1228,362 @@ class AdviseSeccompTracer:
 
     def destroy(self):
         self.map.destroy()
+
+
+# ------------------------------------------------------------------------------------
+# traceloop (pkg/gadgets/traceloop/tracer/tracer.go, syscall_helpers.go, types/types.go)
+# ------------------------------------------------------------------------------------
+USE_NULL_BYTE_LENGTH = 0x0FFFFFFFFFFFFFFF      # traceloop.h:18
+TRACELOOP_SYS_SAMPLE, TRACELOOP_CONT_SAMPLE = 100, 156   # alignSize(96), alignSize(152): tracer.go:86-92
+# struct syscall_event_t / syscall_event_cont_t (traceloop.h:34-55): (name, offset, bytes)
+TRACELOOP_SYS_FIELDS = [("args", 0, 48), ("mono_ts", 48, 8), ("boot_ts", 56, 8), ("pid", 64, 4), ("cpu", 68, 2),
+                        ("id", 70, 2), ("comm", 72, 16), ("cont_nr", 88, 1), ("typ", 89, 1)]
+TRACELOOP_CONT_FIELDS = [("param", 0, 128), ("mono_ts", 128, 8), ("length", 136, 8), ("index", 144, 1),
+                         ("failed", 145, 1)]
+TRACELOOP_SYS_BYTES, TRACELOOP_CONT_BYTES = 96, 152
+
+
+def _traceloop_dtypes():
+    import numpy as np
+    sys_dt = np.dtype({"names": ["args", "mono_ts", "boot_ts", "pid", "cpu", "id", "comm", "cont_nr", "typ"],
+                       "formats": [("<u8", 6), "<u8", "<u8", "<u4", "<u2", "<u2", ("u1", 16), "u1", "u1"],
+                       "offsets": [o for _, o, _ in TRACELOOP_SYS_FIELDS], "itemsize": TRACELOOP_SYS_BYTES})
+    cont_dt = np.dtype({"names": ["param", "mono_ts", "length", "index", "failed"],
+                        "formats": [("u1", 128), "<u8", "<u8", "u1", "u1"],
+                        "offsets": [o for _, o, _ in TRACELOOP_CONT_FIELDS], "itemsize": TRACELOOP_CONT_BYTES})
+    return sys_dt, cont_dt
+
+
+def traceloop_decode(samples):
+    """The size switch of Read's callback (tracer.go:272-348) over raw samples (bytes-likes) in
+    the order readOverWritable delivers them: a sample of 100 bytes is a syscall_event_t, one of
+    156 a syscall_event_cont_t, any other size is dropped.  Returns two numpy structured arrays
+    (fields as TRACELOOP_SYS_FIELDS / TRACELOOP_CONT_FIELDS), each in sample order."""
+    import numpy as np
+    sys_dt, cont_dt = _traceloop_dtypes()
+    s, c = bytearray(), bytearray()
+    for raw in samples:
+        raw = bytes(raw)
+        if len(raw) == TRACELOOP_SYS_SAMPLE:
+            s += raw[:TRACELOOP_SYS_BYTES]
+        elif len(raw) == TRACELOOP_CONT_SAMPLE:
+            c += raw[:TRACELOOP_CONT_BYTES]
+    return np.frombuffer(bytes(s), dtype=sys_dt), np.frombuffer(bytes(c), dtype=cont_dt)
+
+
+_GO_ESC = {7: "\\a", 8: "\\b", 12: "\\f", 10: "\\n", 13: "\\r", 9: "\\t", 11: "\\v", 0x5C: "\\\\", 0x22: '\\"'}
+
+
+def go_quote(b) -> str:
+    """strconv.Quote of a Go string holding the bytes b (str: its UTF-8).  \\a \\b \\f \\n \\r \\t \\v
+    \\\\ \\" are escaped; other bytes below 0x20, 0x7f and every byte of invalid UTF-8 print as \\xNN;
+    printable runes (strconv.IsPrint: categories L, M, N, P, S and U+0020) are kept; other runes
+    print as \\uNNNN below 0x10000 and \\UNNNNNNNN above.  Categories come from unicodedata, so
+    the Unicode version is this interpreter's, not that of the Go release the reference was
+    built with."""
+    import unicodedata
+    b = b.encode("utf-8") if isinstance(b, str) else bytes(b)
+    out, i, n = ['"'], 0, len(b)
+    while i < n:
+        c0 = b[i]
+        r, w = None, 1
+        if c0 < 0x80:
+            r = c0
+        else:     # utf8.DecodeRuneInString: shortest form, no surrogates, at most U+10FFFF
+            need = 2 if 0xC2 <= c0 <= 0xDF else 3 if 0xE0 <= c0 <= 0xEF else 4 if 0xF0 <= c0 <= 0xF4 else 0
+            if need and i + need <= n:
+                try:
+                    r, w = ord(b[i:i + need].decode("utf-8")), need
+                except UnicodeDecodeError:
+                    r = None
+        if r is None:
+            out.append("\\x%02x" % c0)
+        elif r in _GO_ESC:
+            out.append(_GO_ESC[r])
+        elif r == 0x20 or unicodedata.category(chr(r))[0] in "LMNPS":
+            out.append(chr(r))
+        elif r < 0x20 or r == 0x7F:
+            out.append("\\x%02x" % r)
+        elif r < 0x10000:
+            out.append("\\u%04x" % r)
+        else:
+            out.append("\\U%08x" % r)
+        i += w
+    out.append('"')
+    return "".join(out)
+
+
+def _c_bytes(b, limit=None):
+    """gadgets.FromCString / FromCStringN (helpers.go:76-97) on bytes, as bytes."""
+    b = bytes(b)
+    if limit is not None:
+        if limit < 0:
+            raise ValueError("traceloop: cont length converts to a negative int (the reference panics)")
+        b = b[:limit]
+    i = b.find(b"\0")
+    return b if i < 0 else b[:i]
+
+
+def traceloop_cont_param(param, length: int, failed: int) -> str:
+    """A cont record's parameter text (tracer.go:326-336)."""
+    if failed:
+        s = b"(Failed to dereference pointer)"
+    elif length == USE_NULL_BYTE_LENGTH:
+        s = _c_bytes(param)
+    else:
+        s = _c_bytes(param, length - (1 << 64) if length >= 1 << 63 else length)
+    return go_quote(s)
+
+
+@dataclass
+class SyscallDeclaration:
+    """syscall_helpers.go:37-40: params are (position, name)."""
+    name: str
+    params: list = field(default_factory=list)
+
+    def getParameterCount(self) -> int:
+        return len(self.params) & 0xFF
+
+    def getParameterName(self, i: int) -> str:
+        if i >= len(self.params):
+            raise IndexError(f"param number {i} out of bounds for syscall {self.name!r}")
+        return self.params[i][1]
+
+
+_TRACEFS_FIELD = None
+
+
+def parseSyscall(name: str, format_text: str) -> SyscallDeclaration:
+    """syscall_helpers.go:81-167 on the text of a tracefs `format` file: lines up to the first empty
+    one are skipped; after it every line matching `\\s+field:TYPE NAME;` is a parameter, at position
+    line index - 8, except __syscall_nr."""
+    global _TRACEFS_FIELD
+    if _TRACEFS_FIELD is None:
+        import re
+        _TRACEFS_FIELD = re.compile(r"[\t\n\f\r ]+field:(.*?) ([a-z_0-9]+);.*")
+    params, skipped = [], False
+    for idx, line in enumerate(format_text.split("\n")):
+        if not skipped:
+            if len(line) != 0:
+                continue
+            skipped = True
+        m = _TRACEFS_FIELD.search(line)
+        if m is None or m.group(2) == "__syscall_nr":
+            continue
+        params.append((idx - 8, m.group(2)))
+    return SyscallDeclaration(name, params)
+
+
+def relateSyscallName(name: str) -> str:
+    """syscall_helpers.go:120-139: sys_enter_NAME -> the name in asm/unistd_64.h."""
+    return {"newfstat": "fstat", "newlstat": "lstat", "newstat": "stat", "newuname": "uname",
+            "sendfile64": "sendfile", "sysctl": "_sysctl", "umount": "umount2"}.get(name, name)
+
+
+@dataclass
+class SyscallParam:
+    """types.go:26-29."""
+    Name: str = ""
+    Value: str = ""
+
+
+@dataclass
+class TraceloopEvent:
+    """pkg/gadgets/traceloop/types/types.go:31-41 (eventtypes.Event + WithMountNsID flattened)."""
+    Node: str = ""
+    Namespace: str = ""
+    Pod: str = ""
+    Container: str = ""
+    Timestamp: int = 0
+    MountNsID: int = 0
+    CPU: int = 0
+    Pid: int = 0
+    Comm: str = ""
+    Syscall: str = ""
+    Parameters: list = field(default_factory=list)
+    Retval: int = 0
+
+
+_TRACELOOP_NO_EXIT = ("exit", "exit_group", "rt_sigreturn")
+
+
+def TraceloopColumns():
+    """types.GetColumns() (types.go:51-91): the params and ret extractors; node, namespace, pod
+    and container hidden.  Filtering or sorting by an extractor column is not supported, as for
+    every extractor column."""
+    from . import textcolumns as T
+    cm = T.ColumnMap([(a, k, t) for a, k, t, _ in _COMMON_COLS[:4]] +
+                     [("Timestamp", "int64", "timestamp,template:timestamp"), ("MountNsID", "uint64", "mntns,template:ns"),
+                      ("CPU", "uint16", "cpu,width:3,fixed"), ("Pid", "uint32", "pid,template:pid"),
+                      ("Comm", "string", "comm,template:comm"), ("Syscall", "string", "syscall,template:syscall"),
+                      ("Parameters", "string", "params,width:40"), ("Retval", "int", "ret,width:3,fixed")])
+    for a, _, t, tags in _COMMON_COLS[:4]:
+        cm.cols[t.split(",")[0]].Tags = list(tags)
+    cm.SetExtractor("params", lambda ev: ", ".join(f"{p.Name}={p.Value}" for p in ev.Parameters))
+    cm.SetExtractor("ret", lambda ev: "X" if ev.Syscall in _TRACELOOP_NO_EXIT else str(int(ev.Retval)))
+    for name in ("node", "namespace", "pod", "container"):
+        cm.cols[name].Visible = False
+    return cm
+
+
+def traceloop_render(events, terminal_width: int = 0, columns=None) -> str:
+    """The columns output of one Read."""
+    from . import textcolumns as T
+    return T.TransformIntoTable(T.TextColumnsFormatter(TraceloopColumns(), DefaultColumns=columns), events, terminal_width)
+
+
+def traceloop_events(sys, cont, row, exit_row, cls, cont_rows, names, declarations, mntns=None, have_boot_ns=True,
+                     boot_to_wall_ns=0):
+    """The types.Event list of tracer.go:369-530 from the join's columns (host sequences: row,
+    exit_row, cls per event, cont_rows six per event; 0xFFFFFFFF or -1: none) over the decoded
+    records sys / cont (traceloop_decode).  mntns: per syscall row, or one number."""
+    none = (0xFFFFFFFF, -1)
+    out = []
+    for j in range(len(row)):
+        r = sys[int(row[j])]
+        name = names.get(int(r["id"]))
+        if name is None:
+            if int(cls[j]) == 2:
+                continue                                      # :502-507: best effort
+            raise LookupError(f"getting name of syscall number {int(r['id'])}")
+        ts = int(r["boot_ts"]) if have_boot_ns else int(r["mono_ts"])
+        mn = mntns if mntns is None or isinstance(mntns, int) else int(mntns[int(row[j])])
+        ev = TraceloopEvent(Timestamp=(ts + boot_to_wall_ns) if have_boot_ns else 0, MountNsID=mn or 0,
+                            CPU=int(r["cpu"]), Pid=int(r["pid"]), Comm=_c_bytes(r["comm"].tobytes()).decode("utf-8", "replace"),
+                            Syscall=name)
+        if int(cls[j]) == 0:
+            decl = declarations[name]
+            decl = decl if isinstance(decl, SyscallDeclaration) else SyscallDeclaration(name, list(enumerate(decl)))
+            for i in range(decl.getParameterCount()):
+                value = "%d" % int(r["args"][i])              # i >= 6: the reference's slice has six
+                cj = int(cont_rows[6 * j + i]) if i < 6 else -1
+                if cj not in none:
+                    c = cont[cj]
+                    value = traceloop_cont_param(c["param"].tobytes(), int(c["length"]), int(c["failed"]))
+                ev.Parameters.append(SyscallParam(decl.getParameterName(i), value))
+            if int(exit_row[j]) not in none:
+                ev.Retval = int(sys[int(exit_row[j])]["args"][0].astype("int64"))
+        elif int(cls[j]) == 2:
+            ev.Retval = int(r["args"][0].astype("int64"))
+        out.append(ev)
+    return out
+
+
+class TraceloopTracer:
+    """traceloop: the syscall flight recorder.  Attach / Detach / Delete as tracer.go:196-230 and
+    :547-567; feed() stands for the BPF side writing raw samples into a container's ring in the
+    order readOverWritable would deliver them (reading the ring is the caller's); Read(containerID)
+    is Tracer.Read for one container, and ReadAll() runs one device join over the rows of every
+    attached container and splits the events per container afterwards.
+
+    names: {number: name} (default _syscalls.X86_64); declarations: {name: SyscallDeclaration or
+    a list of parameter names} (parseSyscall / relateSyscallName build them from tracefs format
+    files).  have_boot_ns=False is a kernel without bpf_ktime_get_boot_ns: events sort by the
+    monotonic timestamp and carry Timestamp 0 (tracer.go:232-244, :538-542).  boot_to_wall_ns is
+    WallTimeFromBootTime's offset, applied to every timestamp, zero included.  A Read consumes
+    the samples it saw."""
+
+    def __init__(self, declarations, names=None, have_boot_ns=True, boot_to_wall_ns=0, device="cuda"):
+        from ._syscalls import X86_64
+        self.names = dict(X86_64 if names is None else names)
+        self.declarations = dict(declarations)
+        by_name = {v: k for k, v in self.names.items()}
+        self.nr = tuple(by_name.get(n, 0xFFFF) for n in _TRACELOOP_NO_EXIT)
+        self.have_boot_ns, self.boot_to_wall_ns, self.device = have_boot_ns, boot_to_wall_ns, device
+        self.readers: Dict[str, dict] = {}     # containerID -> {"mntns", "samples", "attached"}
+
+    def Attach(self, containerID: str, mntns: int):
+        self.readers[containerID] = {"mntns": int(mntns), "samples": [], "attached": True}
+
+    def Detach(self, mntns: int):
+        """The perf buffer leaves the BPF map: nothing more is recorded for the namespace."""
+        hit = [r for r in self.readers.values() if r["mntns"] == int(mntns) and r["attached"]]
+        if not hit:
+            raise LookupError(f"error removing perf buffer from map with mntnsID {mntns}")
+        for r in hit:
+            r["attached"] = False
+
+    def Delete(self, containerID: str):
+        if self.readers.pop(containerID, None) is None:
+            raise LookupError(f"no reader for containerID {containerID}")
+
+    def feed(self, containerID: str, samples):
+        r = self.readers.get(containerID)
+        if r is None:
+            raise LookupError(f'no perf reader for "{containerID}"')
+        if r["attached"]:
+            r["samples"] += [bytes(s) for s in samples]
+
+    def _device_cols(self, sys, cont):
+        import numpy as np
+        torch = torch_mod()
+        out = []
+        for arr, nbytes, fields in ((sys, TRACELOOP_SYS_BYTES, [("mono_ts", 48, 8, torch.uint64), ("boot_ts", 56, 8, torch.uint64),
+                                                                ("pid", 64, 4, torch.int32), ("id", 70, 2, torch.int16),
+                                                                ("typ", 89, 1, torch.uint8)]),
+                                    (cont, TRACELOOP_CONT_BYTES, [("mono_ts", 128, 8, torch.uint64), ("index", 144, 1, torch.uint8)])):
+            n = len(arr)
+            if n == 0:
+                out.append({f[0]: torch.empty(0, dtype=f[3], device=self.device) for f in fields})
+                continue
+            raw = torch.from_numpy(np.frombuffer(arr.tobytes(), dtype=np.uint8).copy()).to(self.device)
+            out.append(engine.ingest_aos(raw, n, nbytes, fields))
+        return out
+
+    def _check_enters(self, sys):
+        """tracer.go:364-384: an enter without a name or a declaration fails the whole Read."""
+        for i in sorted({int(x) for x in sys["id"][sys["typ"] == 0]}):
+            name = self.names.get(i)
+            if name is None:
+                raise LookupError(f"getting name of syscall number {i}")
+            if name not in self.declarations:
+                raise LookupError("getting syscall definition")
+
+    def _join(self, sys, cont, mntns_s=None, mntns_c=None):
+        torch = torch_mod()
+        self._check_enters(sys)
+        if len(sys) == 0:
+            return []
+        ds, dc = self._device_cols(sys, cont)
+        dev_mn = lambda a: None if a is None else torch.from_numpy(a.view("int64")).to(self.device)   # noqa: E731
+        j = engine.traceloop_join(ds["mono_ts"], ds["boot_ts"] if self.have_boot_ns else ds["mono_ts"], ds["typ"],
+                                  ds["id"], ds["pid"], mntns=dev_mn(mntns_s), c_mono_ts=dc["mono_ts"],
+                                  c_index=dc["index"], c_mntns=dev_mn(mntns_c), nr=self.nr)
+        return j
+
+    def Read(self, containerID: str) -> List[TraceloopEvent]:
+        r = self.readers.get(containerID)
+        if r is None:
+            raise LookupError(f'no perf reader for "{containerID}"')
+        sys, cont = traceloop_decode(r["samples"])
+        j = self._join(sys, cont)
+        r["samples"] = []
+        if not len(sys):
+            return []
+        return traceloop_events(sys, cont, host(j["row"]), host(j["exit"]), host(j["cls"]), host(j["cont"]).reshape(-1),
+                                self.names, self.declarations, r["mntns"], self.have_boot_ns, self.boot_to_wall_ns)
+
+    def ReadAll(self) -> Dict[str, List[TraceloopEvent]]:
+        """One join over every container's rows; {containerID: events}.  An enter without a name
+        or a declaration in any container fails the call."""
+        import numpy as np
+        ids = list(self.readers)
+        dec = [traceloop_decode(self.readers[c]["samples"]) for c in ids]
+        # one decode of every container's samples (np.concatenate would repack the padded records)
+        sys, cont = traceloop_decode([s for c in ids for s in self.readers[c]["samples"]])
+        mn = lambda k: np.concatenate([np.full(len(d[k]), self.readers[c]["mntns"], np.uint64)   # noqa: E731
+                                       for c, d in zip(ids, dec)]) if dec else np.zeros(0, np.uint64)
+        mntns_s, mntns_c = mn(0), mn(1)
+        owner = np.concatenate([np.full(len(d[0]), i, np.int64) for i, d in enumerate(dec)]) if dec else np.zeros(0, np.int64)
+        j = self._join(sys, cont, mntns_s, mntns_c)
+        for c in ids:
+            self.readers[c]["samples"] = []
+        out = {c: [] for c in ids}
+        if not len(sys):
+            return out
+        row, ex, cls, cr = host(j["row"]), host(j["exit"]), host(j["cls"]), host(j["cont"]).reshape(-1, 6)
+        for i, c in enumerate(ids):
+            sel = np.nonzero(owner[row] == i)[0]
+            out[c] = traceloop_events(sys, cont, row[sel], ex[sel], cls[sel], cr[sel].reshape(-1), self.names,
+                                      self.declarations, self.readers[c]["mntns"], self.have_boot_ns, self.boot_to_wall_ns)
+        return out
