@@ -558,6 +558,51 @@ int igx_req_join(igx_ctx *ctx, const uint64_t *req, const uint8_t *kind, const u
                  uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend);
 int igx_req_join_tile(void);
 
+/* ---- the two-register last-writer join ---------------------------------------------------- */
+/* The join that the gadgets of pkg/gadgets/trace/ run when they pair a kprobe with its kretprobe
+ * through hash maps keyed by the thread.  trace capabilities
+ * (pkg/gadgets/trace/capabilities/tracer/bpf/capable.bpf.c) keeps two maps under pid_tgid:
+ * `start` (:40-45) holds the arguments of the pending cap_capable call -- the kprobe writes it
+ * (:147), the kretprobe looks it up (:162-164: without it, "missed entry", it returns at once)
+ * and deletes it (:193); `current_syscall` (:80-85) holds the syscall the thread is in --
+ * sys_enter writes it (:237), sys_exit deletes it (:246), and the kretprobe only reads it
+ * (:184-189).  Unlike igx_req_join's who entry, the second entry survives any number of reads,
+ * and nothing here is deleted conditionally: it is a last-writer machine with two registers, A
+ * and B, per key.
+ *
+ * A batch is nrows rows in stream order (row i before row i + 1): key (u64), kind (u8, enum
+ * igx_lw_kind); rows with valid[i] == 0 (valid nullable) or any other kind do not exist for the
+ * join (the filters a probe applies before it touches the maps).  Every key starts the batch with
+ * both registers empty.  Per key, in row order:
+ *   IGX_LW_SET_A    A := this row (overwrites; capable.bpf.c:147)
+ *   IGX_LW_SET_B    B := this row (overwrites; :237)
+ *   IGX_LW_CLEAR_B  B := empty (:246)
+ *   IGX_LW_TAKE_A   with A empty: nothing, and B is untouched (:162-164); else emit (this row,
+ *                   the A row, the B row or IGX_NO_COL) and A := empty (:193); B is not changed
+ * take_row, a_row, b_row (device, nrows entries each): entry j describes the j-th emitting TAKE_A
+ * in stream order; igx_take of a b_row of IGX_NO_COL yields a zero row, so a caller for whom zero
+ * is a value (syscall 0) masks on b_row itself.  *d_ntake (device u64) is their number; entries
+ * at and past it are unspecified.  The rows still held in a register at the end of the batch --
+ * per key at most one A row and one B row -- go to pend_row in stream order: nothing is written
+ * past pend_cap entries, and *d_npend (device u64) is their true number, which may exceed
+ * pend_cap.  State crosses a batch boundary in band: put those rows, every column, in that order,
+ * in front of the next batch.  The maps' max_entries are not reproduced.  The one-register
+ * gadgets of the family are the special case SET_A / TAKE_A.
+ *
+ * nrows <= 2^32 - 2 (IGX_EINVAL otherwise, checked before anything else is looked at); 0 is
+ * valid.  key and the counts are 8-byte aligned, the row outputs 4-byte aligned (IGX_EINVAL
+ * otherwise).  The outputs may not overlap the inputs or each other.  Work per row does not
+ * depend on how long a key's run is; scratch of about 10 bytes per row beside the sort's
+ * (IGX_ENOMEM if it cannot be had, and nothing stays allocated).  One host synchronisation (the
+ * sort's digit plan); the counts stay on the device.  igx_lw_join_tile: the rows per tile of the
+ * device scan (sizes around it are where tiles hand state over). */
+enum igx_lw_kind { IGX_LW_SET_A = 0, IGX_LW_SET_B = 1, IGX_LW_CLEAR_B = 2, IGX_LW_TAKE_A = 3 };
+int igx_lw_join(igx_ctx *ctx, const uint64_t *key, const uint8_t *kind,
+                const uint8_t *valid /*nullable*/, uint64_t nrows,
+                uint32_t *take_row, uint32_t *a_row, uint32_t *b_row, uint64_t *d_ntake,
+                uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend);
+int igx_lw_join_tile(void);
+
 /* ---- profile cpu: row interning, symbol lookup -------------------------------------------- */
 /* profile cpu (pkg/gadgets/profile/cpu/tracer/bpf/profile.bpf.c:60-114) keys its counts by
  * key_t (profile.h:9-16), whose two stack fields are ids: bpf_get_stackid (:93, :98) turns a
@@ -600,11 +645,21 @@ int igx_req_join_tile(void);
  * row's home slot is hash & (S - 1), probing is linear from there, and a slot carries the tag
  * hash >> 32: a candidate row is compared only where the tags agree.  Rows equal in both and
  * different in content are the table's worst case, and these two statements let a caller build
- * them. */
+ * them.
+ *
+ * igx_intern_add_first does what igx_intern_add does -- the same store, the same ids -- and
+ * writes out_first (device u8, nrows entries): 1 iff row i is valid and is the first valid
+ * occurrence, over all calls on the object, of its content; 0 otherwise.  That is the `seen` map
+ * of trace capabilities' --unique (capable.bpf.c:128-139: only the first cap_capable of a (cap,
+ * mntns) passes).  The mask is a function of the stream alone: any split into batches gives the
+ * same mask.  out_ids may be NULL here (the ids are then not written).  After overflow the mask
+ * is unspecified, as the ids are. */
 typedef struct igx_intern igx_intern;
 int igx_intern_create(igx_ctx *ctx, uint32_t row_bytes, uint64_t capacity, igx_intern **out);
 int igx_intern_add(igx_intern *t, const void *rows, uint64_t row_stride, const uint8_t *valid /*nullable*/,
                    uint64_t nrows, uint32_t *out_ids);
+int igx_intern_add_first(igx_intern *t, const void *rows, uint64_t row_stride, const uint8_t *valid /*nullable*/,
+                         uint64_t nrows, uint32_t *out_ids /*nullable*/, uint8_t *out_first);
 int igx_intern_count(igx_intern *t, uint64_t *n_distinct);
 int igx_intern_rows(igx_intern *t, const uint32_t *ids, uint64_t k, void *out);
 int igx_intern_slots(igx_intern *t, uint64_t *n_slots);

@@ -31,6 +31,7 @@ AGG_COUNT, AGG_SUM = 0, 1
 FILTER_ANY, FILTER_NIL_MATCH = 1, 2
 GB_AUTO, GB_CACHED, GB_DIRECT, GB_PART = 0, 1, 2, 3
 REQ_START, REQ_ISSUE, REQ_DONE = 0, 1, 2
+LW_SET_A, LW_SET_B, LW_CLEAR_B, LW_TAKE_A = 0, 1, 2, 3
 SECCOMP_SYSCALLS, SECCOMP_VALUE_BYTES = 500, 501
 
 
@@ -167,8 +168,11 @@ SIGNATURES = [
     ("igx_log2_slots", _I, [_VP, _VP, _U64, _U64, _U32, _VP, _VP]),
     ("igx_req_join", _I, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _VP, _VP, _VP, _U64, _VP]),
     ("igx_req_join_tile", _I, []),
+    ("igx_lw_join", _I, [_VP, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _VP, _VP, _U64, _VP]),
+    ("igx_lw_join_tile", _I, []),
     ("igx_intern_create", _I, [_VP, _U32, _U64, C.POINTER(_VP)]),
     ("igx_intern_add", _I, [_VP, _VP, _U64, _VP, _U64, _VP]),
+    ("igx_intern_add_first", _I, [_VP, _VP, _U64, _VP, _U64, _VP, _VP]),
     ("igx_intern_count", _I, [_VP, C.POINTER(_U64)]),
     ("igx_intern_rows", _I, [_VP, _VP, _U64, _VP]),
     ("igx_intern_slots", _I, [_VP, C.POINTER(_U64)]),

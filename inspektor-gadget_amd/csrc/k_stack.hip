@@ -333,8 +333,12 @@ extern "C" int igx_intern_slots(igx_intern *t, uint64_t *n_slots) {
     return IGX_OK;
 }
 
-extern "C" int igx_intern_add(igx_intern *t, const void *rows, uint64_t row_stride, const uint8_t *valid,
-                              uint64_t nrows, uint32_t *out_ids) {
+// igx_intern_add and igx_intern_add_first.  The flag pass already marks a content's first
+// occurrence over the whole stream (the row its slot still refers to): with out_first the flags
+// are written there instead of to scratch.  Without out_ids the slot numbers go to scratch and
+// the last pass, which turns them into ids, is left out.
+static int intern_add(igx_intern *t, const void *rows, uint64_t row_stride, const uint8_t *valid, uint64_t nrows,
+                      uint32_t *out_ids, uint8_t *out_first, bool want_first) {
     if (!t) return IGX_EINVAL;
     igx_ctx *ctx = t->ctx;
     if (nrows > 0x7FFFFFFFull) return igx_fail(ctx, IGX_EINVAL, "intern_add: more than 2^31 - 1 rows");
@@ -343,19 +347,22 @@ extern "C" int igx_intern_add(igx_intern *t, const void *rows, uint64_t row_stri
     if ((uintptr_t)rows & 7) return igx_fail(ctx, IGX_EINVAL, "intern_add: rows must be 8-byte aligned");
     if ((uintptr_t)out_ids & 3) return igx_fail(ctx, IGX_EINVAL, "intern_add: out_ids must be 4-byte aligned");
     if (nrows == 0) return IGX_OK;
-    if (!rows || !out_ids) return igx_fail(ctx, IGX_EINVAL, "intern_add: null argument");
+    if (!rows || (want_first ? !out_first : !out_ids)) return igx_fail(ctx, IGX_EINVAL, "intern_add: null argument");
 
     const uint64_t tiles = (nrows + CTILE - 1) / CTILE;
     const size_t flag_b = igx_align(nrows, 256), cnt_b = igx_align(tiles * 4, 256);
     const size_t off_b = igx_align(tiles * 8, 256), new_b = igx_align(nrows * 4, 256);
+    const size_t slot_b = out_ids ? 0 : new_b;
     void *s;
-    const int rc = igx_scratch(ctx, flag_b + cnt_b + off_b + new_b, &s);
+    const int rc = igx_scratch(ctx, flag_b + cnt_b + off_b + new_b + slot_b, &s);
     if (rc) return rc;
     char *c = reinterpret_cast<char *>(s);
-    uint8_t *flags = reinterpret_cast<uint8_t *>(c);
+    uint8_t *flags = out_first ? out_first : reinterpret_cast<uint8_t *>(c);
     uint32_t *cnt = reinterpret_cast<uint32_t *>(c + flag_b);
     uint64_t *off = reinterpret_cast<uint64_t *>(c + flag_b + cnt_b);
     uint32_t *newrows = reinterpret_cast<uint32_t *>(c + flag_b + cnt_b + off_b);
+    const bool ids = out_ids != nullptr;
+    if (!ids) out_ids = reinterpret_cast<uint32_t *>(c + flag_b + cnt_b + off_b + new_b);
     const uint8_t *in = reinterpret_cast<const uint8_t *>(rows);
 
     hipLaunchKernelGGL(k_st_insert, dim3(wave_grid(ctx, nrows)), dim3(TB), 0, ctx->stream, in, row_stride, valid, nrows,
@@ -366,10 +373,21 @@ extern "C" int igx_intern_add(igx_intern *t, const void *rows, uint64_t row_stri
                        t->state, t->cap, t->slots, newrows);
     hipLaunchKernelGGL(k_st_copy, dim3(wave_grid(ctx, std::min(nrows, t->cap))), dim3(TB), 0, ctx->stream, in,
                        row_stride, t->row_bytes, newrows, t->state, t->cap, t->store);
-    hipLaunchKernelGGL(k_st_gather, dim3((unsigned)((nrows + TB - 1) / TB)), dim3(TB), 0, ctx->stream, t->slots, nrows,
-                       out_ids);
+    if (ids)
+        hipLaunchKernelGGL(k_st_gather, dim3((unsigned)((nrows + TB - 1) / TB)), dim3(TB), 0, ctx->stream, t->slots,
+                           nrows, out_ids);
     IGX_HIP(ctx, hipGetLastError());
     return IGX_OK;
+}
+
+extern "C" int igx_intern_add(igx_intern *t, const void *rows, uint64_t row_stride, const uint8_t *valid,
+                              uint64_t nrows, uint32_t *out_ids) {
+    return intern_add(t, rows, row_stride, valid, nrows, out_ids, nullptr, false);
+}
+
+extern "C" int igx_intern_add_first(igx_intern *t, const void *rows, uint64_t row_stride, const uint8_t *valid,
+                                    uint64_t nrows, uint32_t *out_ids, uint8_t *out_first) {
+    return intern_add(t, rows, row_stride, valid, nrows, out_ids, out_first, true);
 }
 
 extern "C" int igx_intern_count(igx_intern *t, uint64_t *n_distinct) {

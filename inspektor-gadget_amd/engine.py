@@ -554,6 +554,47 @@ def req_join(req, kind, ts, valid=None, pend_cap=None, sync=True):
 
 
 # ------------------------------------------------------------------------------------
+# the two-register last-writer join (kprobe / kretprobe pairs keyed by the thread)
+# ------------------------------------------------------------------------------------
+def lw_join_tile():
+    """igx_lw_join_tile: rows per tile of the join's device scan (host call, no GPU)."""
+    return int(_abi.lib().igx_lw_join_tile())
+
+
+def lw_join(key, kind, valid=None, pend_cap=None, sync=True):
+    """igx_lw_join: the last-writer join with two registers per key (capable.bpf.c:87-248; the
+    contract is in include/igx.h).  key: u64 (or int64) device tensor, kind (_abi.LW_*) and valid:
+    uint8, all of n rows in stream order.
+    Returns a dict: take, a, b (int32 row ids; b is -1, i.e. IGX_NO_COL, with B empty), one entry
+    per emitting TAKE_A in stream order; pend, the rows still held in a register at the end, in
+    stream order (at most pend_cap of them, default n); n_take and n_pend, the true counts.
+    sync=True reads the counts (one host read) and trims the tensors; sync=False returns
+    full-capacity tensors and the counts as device u64 tensors."""
+    torch = torch_mod()
+    ctx = context()
+    n = int(key.numel())
+    cap = n if pend_cap is None else int(pend_cap)
+    dev = key.device
+    key, kind = key.contiguous(), kind.contiguous()
+    valid = None if valid is None else valid.contiguous()
+    m = max(1, n)
+    take_, a, b = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(3))
+    pend = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
+    cnt = torch.empty(2, dtype=torch.uint64, device=dev)
+    ctx.check(ctx.L.igx_lw_join(ctx.h, ptr(key), ptr(kind), ptr(valid), n, ptr(take_), ptr(a), ptr(b),
+                                C.c_void_p(cnt.data_ptr()), ptr(pend), cap, C.c_void_p(cnt.data_ptr() + 8)))
+    out = {"take": take_[:n], "a": a[:n], "b": b[:n], "pend": pend[:cap], "n_take": cnt[0:1], "n_pend": cnt[1:2]}
+    if not sync:
+        return out
+    nt, npend = (int(x) for x in cnt.cpu().view(torch.int64))
+    for k in ("take", "a", "b"):
+        out[k] = out[k][:nt]
+    out["pend"] = out["pend"][:min(npend, cap)]
+    out["n_take"], out["n_pend"] = nt, npend
+    return out
+
+
+# ------------------------------------------------------------------------------------
 # traceloop: the enter / exit / cont join by timestamp
 # ------------------------------------------------------------------------------------
 TRACELOOP_NR_X86_64 = (60, 231, 15)    # exit, exit_group, rt_sigreturn (traceloop.bpf.c:12-35)
@@ -630,16 +671,21 @@ class Interner:
         self.h = h
         self.row_bytes, self.capacity = row_bytes, capacity
 
-    def add(self, rows, valid=None):
+    def add(self, rows, valid=None, first=False):
         """igx_intern_add (asynchronous): int32 ids of the rows (-1, i.e. IGX_NO_COL, where
-        valid is 0)."""
+        valid is 0).  first=True (igx_intern_add_first) returns (ids, first): first is uint8, 1
+        where the row is the first valid occurrence of its content over all calls."""
         torch = torch_mod()
         self.ctx.bind_stream()
         rows, stride, n = _row_view(rows, self.row_bytes)
         valid = None if valid is None else valid.contiguous()
         out = torch.empty(max(1, n), dtype=torch.int32, device=rows.device)
-        self.ctx.check(self.ctx.L.igx_intern_add(self.h, ptr(rows), stride, ptr(valid), n, ptr(out)))
-        return out[:n]
+        if not first:
+            self.ctx.check(self.ctx.L.igx_intern_add(self.h, ptr(rows), stride, ptr(valid), n, ptr(out)))
+            return out[:n]
+        mask = torch.empty(max(1, n), dtype=torch.uint8, device=rows.device)
+        self.ctx.check(self.ctx.L.igx_intern_add_first(self.h, ptr(rows), stride, ptr(valid), n, ptr(out), ptr(mask)))
+        return out[:n], mask[:n]
 
     def count(self):
         """igx_intern_count (synchronises): distinct rows stored; IgxError(IGX_ENOSPC) once the

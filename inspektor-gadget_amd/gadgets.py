@@ -1,5 +1,6 @@
 """The aggregation gadgets as their tracers expose them: top tcp / file / block-io,
-profile block-io / cpu, advise seccomp-profile and traceloop, on top of libigx.so.
+profile block-io / cpu, advise seccomp-profile, traceloop and trace capabilities, on top of
+libigx.so.
 
 Each `Top*` class is the user-space half of a reference tracer plus the BPF map update it
 drains, re-cut for batches of events resident in HBM:
@@ -23,6 +24,8 @@ References (paths under the reference root):
                 tracer/gadget.go:85-143 (reportToString), bpf/biolatency.bpf.c:100-154
   profile cpu   pkg/gadgets/profile/cpu/tracer/bpf/profile.bpf.c:60-114, tracer/tracer.go:86-322,
                 types/types.go:27-56
+  trace capabilities  pkg/gadgets/trace/capabilities/tracer/bpf/capable.bpf.c:87-248,
+                tracer/tracer.go:224-318, types/types.go:35-73
 
 The reference's pre-sort order (BPF hash iteration) is replaced by each group's first
 event index; everything else -- keys, wrap widths, sort order including
@@ -1587,3 +1590,233 @@ class TraceloopTracer:
             out[c] = traceloop_events(sys, cont, row[sel], ex[sel], cls[sel], cr[sel].reshape(-1), self.names,
                                       self.declarations, self.readers[c]["mntns"], self.have_boot_ns, self.boot_to_wall_ns)
         return out
+
+
+# ------------------------------------------------------------------------------------
+# trace capabilities (pkg/gadgets/trace/capabilities)
+# ------------------------------------------------------------------------------------
+CAP_ENTER, CAP_EXIT, SYS_ENTER, SYS_EXIT = 0, 1, 2, 3      # the four probes of capable.bpf.c, as batch kinds
+
+# The kernel's capability names (include/uapi/linux/capability.h, CAP_CHOWN = 0 ..
+# CAP_CHECKPOINT_RESTORE = 40) without their prefix: CapName is the upper-case form
+# (tracer.go:59-101) and CapsNames the lower-case one.
+CAPABILITY_NAMES = (
+    "CHOWN", "DAC_OVERRIDE", "DAC_READ_SEARCH", "FOWNER", "FSETID", "KILL", "SETGID", "SETUID", "SETPCAP",
+    "LINUX_IMMUTABLE", "NET_BIND_SERVICE", "NET_BROADCAST", "NET_ADMIN", "NET_RAW", "IPC_LOCK", "IPC_OWNER",
+    "SYS_MODULE", "SYS_RAWIO", "SYS_CHROOT", "SYS_PTRACE", "SYS_PACCT", "SYS_ADMIN", "SYS_BOOT", "SYS_NICE",
+    "SYS_RESOURCE", "SYS_TIME", "SYS_TTY_CONFIG", "MKNOD", "LEASE", "AUDIT_WRITE", "AUDIT_CONTROL", "SETFCAP",
+    "MAC_OVERRIDE", "MAC_ADMIN", "SYSLOG", "WAKE_ALARM", "BLOCK_SUSPEND", "AUDIT_READ", "PERFMON", "BPF",
+    "CHECKPOINT_RESTORE")
+CAP_LAST_CAP = len(CAPABILITY_NAMES) - 1
+
+CAPABILITIES_SKIP_NR = {"amd64": (60, 231, 15), "arm64": (93, 94, 139)}   # exit, exit_group, rt_sigreturn (:202-212)
+CAPABILITIES_COLS = ("kind", "pid_tgid", "mntns", "ts", "nr", "cap", "cap_opt", "cred_is_real", "current_userns",
+                     "target_userns", "cap_effective", "ret", "uid", "comm")
+
+
+def kernelVersion(a: int, b: int, c: int) -> int:
+    """tracer.go:224-230 (the KERNEL_VERSION macro)."""
+    return (a << 16) + (b << 8) + min(c, 255)
+
+
+def capabilityName(cap: int) -> str:
+    """tracer.go:259-265."""
+    return CAPABILITY_NAMES[cap] if 0 <= cap <= CAP_LAST_CAP else f"UNKNOWN ({cap})"
+
+
+def capsNames(capsBitField: int) -> List[str]:
+    """tracer.go:232-241: the lower-case names of the bits set, up to CAP_LAST_CAP."""
+    return [CAPABILITY_NAMES[i].lower() for i in range(CAP_LAST_CAP + 1) if (1 << i) & capsBitField]
+
+
+@dataclass
+class CapabilitiesEvent:
+    """pkg/gadgets/trace/capabilities/types/types.go:35-52 (eventtypes.Event + WithMountNsID
+    flattened).  InsetID is None on kernels before 5.1.0."""
+    Node: str = ""
+    Namespace: str = ""
+    Pod: str = ""
+    Container: str = ""
+    Timestamp: int = 0
+    MountNsID: int = 0
+    Pid: int = 0
+    Comm: str = ""
+    Syscall: str = ""
+    UID: int = 0
+    Cap: int = 0
+    CapName: str = ""
+    Audit: int = 0
+    Verdict: str = ""
+    InsetID: Optional[bool] = None
+    TargetUserNs: int = 0
+    CurrentUserNs: int = 0
+    Caps: int = 0
+    CapsNames: list = field(default_factory=list)
+
+
+def capabilities_event(kernel_version: int, names, pid, uid, mntns, comm, ret, ts, current_userns, target_userns,
+                       cap_effective, cap, cap_opt, syscall, boot_to_wall_ns=0) -> CapabilitiesEvent:
+    """tracer.go:257-318 for one cap_event; syscall -1 (no current_syscall entry, or a number
+    without a name) renders ""."""
+    if kernel_version >= kernelVersion(5, 1, 0):
+        audit = 1 if (cap_opt & 0b10) == 0 else 0
+        inset = (cap_opt & 0b100) != 0
+    else:
+        audit, inset = cap_opt, None
+    nr = int(syscall) & 0xFFFFFFFF                    # libseccomp.ScmpSyscall is an int32
+    nr = nr - (1 << 32) if nr >= 1 << 31 else nr
+    return CapabilitiesEvent(Timestamp=int(ts) + boot_to_wall_ns, MountNsID=int(mntns), Pid=int(pid),
+                             Comm=FromCString(comm), Syscall=names.get(nr, "") if nr >= 0 else "", UID=int(uid),
+                             Cap=int(cap), CapName=capabilityName(int(cap)), Audit=int(audit),
+                             Verdict="Allow" if int(ret) == 0 else "Deny", InsetID=inset,
+                             TargetUserNs=int(target_userns), CurrentUserNs=int(current_userns),
+                             Caps=int(cap_effective), CapsNames=capsNames(int(cap_effective)))
+
+
+def CapabilitiesColumns():
+    """types.GetColumns() (types.go:54-73): the insetid, caps and capsnames extractors."""
+    from . import textcolumns as T
+    cm = T.ColumnMap([(a, k, t) for a, k, t, _ in _COMMON_COLS[:4]] +
+                     [("Timestamp", "int64", "timestamp,template:timestamp"), ("MountNsID", "uint64", "mntns,template:ns"),
+                      ("Pid", "uint32", "pid,template:pid"), ("Comm", "string", "comm,template:comm"),
+                      ("Syscall", "string", "syscall,template:syscall"), ("UID", "uint32", "uid,minWidth:6"),
+                      ("Cap", "int", "cap,width:3,fixed"), ("CapName", "string", "capName,width:18,fixed"),
+                      ("Audit", "int", "audit,minWidth:5"), ("Verdict", "string", "verdict,width:7,fixed"),
+                      ("InsetID", "bool", "insetid,width:7,fixed,hide"),
+                      ("TargetUserNs", "uint64", "targetuserns,template:ns"),
+                      ("CurrentUserNs", "uint64", "currentuserns,template:ns"), ("Caps", "uint64", "caps,hide"),
+                      ("CapsNames", "string", "capsnames,hide")])
+    for a, _, t, tags in _COMMON_COLS[:4]:
+        cm.cols[t.split(",")[0]].Tags = list(tags)
+    cm.SetExtractor("insetid", lambda ev: "N/A" if ev.InsetID is None else ("true" if ev.InsetID else "false"))
+    cm.SetExtractor("caps", lambda ev: "%x" % ev.Caps)
+    cm.SetExtractor("capsnames", lambda ev: ",".join(ev.CapsNames))
+    for name in ("node", "namespace", "pod", "container"):
+        cm.cols[name].Visible = False
+    return cm
+
+
+def capabilities_render(events, terminal_width: int = 0, columns=None) -> str:
+    """The columns output of a list of events."""
+    from . import textcolumns as T
+    return T.TransformIntoTable(T.TextColumnsFormatter(CapabilitiesColumns(), DefaultColumns=columns), events,
+                                terminal_width)
+
+
+class TraceCapabilitiesTracer:
+    """trace capabilities from its four probes' own rows (capable.bpf.c:87-248), joined on the
+    device by igx_lw_join: the cap_capable kprobe is SET_A on the thread's `start` entry, its
+    kretprobe TAKE_A, sys_enter SET_B on `current_syscall` and sys_exit CLEAR_B.
+
+    feed(batch) takes device columns (CAPABILITIES_COLS) of probe rows in stream order: kind
+    (uint8: CAP_ENTER, CAP_EXIT, SYS_ENTER, SYS_EXIT), pid_tgid, mntns, ts (boot ns), nr,
+    current_userns, target_userns, cap_effective (u64), cap, cap_opt, ret (i32), uid (u32),
+    cred_is_real (u8: cred == real_cred, :101-107), comm ((n, 16) u8).  It applies the probes' own
+    filters, --unique through igx_intern_add_first on (cap, mntns), joins, gathers the events on
+    the device and returns them in stream order.  Rows still held in a map after a batch are
+    carried into the next one; more than pending_cap of them raises IgxError(IGX_ENOSPC).
+
+    kernel_version: (a, b, c) or a version code.  names: {number: name} for Syscall (default
+    _syscalls.X86_64); goarch selects the numbers sys_enter skips.  my_pid / targ_pid: -1 is
+    "none", as the BPF constants.  mntns_filter: an iterable of mount namespace ids, or None.
+    boot_to_wall_ns: WallTimeFromBootTime's offset."""
+
+    def __init__(self, Unique=False, AuditOnly=True, kernel_version=(5, 15, 0), mntns_filter=None, my_pid=-1,
+                 targ_pid=-1, goarch="amd64", seen_capacity=1 << 16, names=None, pending_cap=1 << 20,
+                 boot_to_wall_ns=0, device="cuda"):
+        from ._syscalls import X86_64
+        self.Unique, self.AuditOnly = bool(Unique), bool(AuditOnly)
+        self.kernel_version = kernel_version if isinstance(kernel_version, int) else kernelVersion(*kernel_version)
+        self.mntns_filter = None if mntns_filter is None else sorted(int(x) for x in mntns_filter)
+        self.my_pid, self.targ_pid = int(my_pid), int(targ_pid)
+        if goarch not in CAPABILITIES_SKIP_NR:
+            raise ValueError("The trace capabilities gadget is not supported on your architecture.")
+        self.skip_nr = CAPABILITIES_SKIP_NR[goarch]
+        self.names = dict(X86_64 if names is None else names)
+        self.pending_cap, self.boot_to_wall_ns, self.device = int(pending_cap), int(boot_to_wall_ns), device
+        self._seen = engine.Interner(16, int(seen_capacity)) if self.Unique else None
+        self._carry = None            # {column: tensor} of the rows still in `start` / `current_syscall`
+
+    def _valid(self, c):
+        """The probes' filters, in their order, as one uint8 mask over the new rows."""
+        torch = torch_mod()
+        i64 = lambda t: t.view(torch.int64) if t.dtype == torch.uint64 else t.to(torch.int64)   # noqa: E731
+        kind = c["kind"]
+        cap_e, sys_e = kind == CAP_ENTER, kind == SYS_ENTER
+        in_ns = None
+        if self.mntns_filter is not None:              # :98-99, :229-230
+            import numpy as np
+            ids = torch.from_numpy(np.array(self.mntns_filter, np.uint64).view(np.int64)).to(kind.device)
+            in_ns = torch.isin(i64(c["mntns"]), ids)
+        pid = (i64(c["pid_tgid"]) >> 32) & 0xFFFFFFFF
+        ok_cap = c["cred_is_real"] != 0                                         # :101-107
+        ok_cap &= pid != (self.my_pid & 0xFFFFFFFF)                             # :112-113 (pid is a __u32)
+        if self.targ_pid != -1:
+            ok_cap &= pid == (self.targ_pid & 0xFFFFFFFF)                       # :115-116
+        if self.AuditOnly:                                                      # :118-126
+            opt = c["cap_opt"].to(torch.int64)
+            ok_cap &= ((opt & 0b10) == 0) if self.kernel_version >= kernelVersion(5, 1, 0) else (opt != 0)
+        nr = i64(c["nr"]) & 0xFFFFFFFF                                          # skip_exit_probe(int nr), :214-218
+        ok_sys = (nr != self.skip_nr[0]) & (nr != self.skip_nr[1]) & (nr != self.skip_nr[2])
+        if in_ns is not None:
+            ok_cap &= in_ns
+            ok_sys &= in_ns
+        return (torch.where(cap_e, ok_cap, torch.where(sys_e, ok_sys, kind <= SYS_EXIT))).to(torch.uint8)
+
+    def _unique(self, c, valid):
+        """:128-139: of the CAP_ENTER rows that passed the filters, only the first of each
+        (cap, mntns) stays; the others return before `start` is written."""
+        torch = torch_mod()
+        cap_e = (c["kind"] == CAP_ENTER) & (valid != 0)
+        rows = torch.stack([c["cap"].to(torch.int64) & 0xFFFFFFFF,
+                            c["mntns"].view(torch.int64) if c["mntns"].dtype == torch.uint64 else c["mntns"].to(torch.int64)],
+                           dim=1).contiguous().view(torch.uint8)
+        _, first = self._seen.add(rows, cap_e.to(torch.uint8), first=True)
+        return torch.where(c["kind"] == CAP_ENTER, first, valid)
+
+    def feed(self, batch: dict, n: Optional[int] = None) -> List[CapabilitiesEvent]:
+        torch = torch_mod()
+        n = int(batch["kind"].shape[0]) if n is None else n
+        c = {k: batch[k][:n] for k in CAPABILITIES_COLS}
+        valid = self._valid(c)
+        if self.Unique and n:
+            valid = self._unique(c, valid)
+        if self._carry is not None:
+            # the carried rows were admitted when they came: they pass no filter and no unique gate again
+            valid = torch.cat([torch.ones(self._carry["kind"].shape[0], dtype=torch.uint8, device=valid.device), valid])
+            c = {k: _cat_rows(self._carry[k], v) for k, v in c.items()}
+        if c["kind"].shape[0] == 0:
+            return []
+        lut = torch.tensor([_abi.LW_SET_A, _abi.LW_TAKE_A, _abi.LW_SET_B, _abi.LW_CLEAR_B] + [255] * 252,
+                           dtype=torch.uint8, device=c["kind"].device)
+        j = engine.lw_join(c["pid_tgid"], lut[c["kind"].to(torch.int64)], valid, pend_cap=self.pending_cap)
+        if j["n_pend"] > self.pending_cap:
+            raise _abi.IgxError(_abi.IGX_ENOSPC, f"trace capabilities: {j['n_pend']} map entries exceed "
+                                                 f"pending_cap={self.pending_cap}")
+        names = list(c)
+        carry = dict(zip(names, engine.take([c[k] for k in names], j["pend"])))
+        self._carry = carry if j["n_pend"] else None
+        if j["n_take"] == 0:
+            return []
+        pid_tgid, uid, mntns, comm, ret, ts = engine.take([c[k] for k in ("pid_tgid", "uid", "mntns", "comm", "ret", "ts")],
+                                                          j["take"])
+        cur, tgt, eff, cap, opt = engine.take([c[k] for k in ("current_userns", "target_userns", "cap_effective", "cap",
+                                                              "cap_opt")], j["a"])
+        nr, = engine.take([c["nr"]], j["b"], pad=True)
+        # :184-189: without a current_syscall entry the syscall is -1; the gathered zero row would read as syscall 0
+        nr = torch.where(j["b"] == -1, torch.full_like(nr.view(torch.int64), -1), nr.view(torch.int64))
+        h = [host(t) for t in (pid_tgid, uid, mntns, comm, ret, ts, cur, tgt, eff, cap, opt, nr)]
+        return [capabilities_event(self.kernel_version, self.names, int(h[0][i]) >> 32, h[1][i], h[2][i],
+                                   h[3][i].tobytes(), h[4][i], h[5][i], h[6][i], h[7][i], h[8][i], h[9][i], h[10][i],
+                                   h[11][i], self.boot_to_wall_ns) for i in range(len(h[0]))]
+
+    @property
+    def pending(self):
+        """Map entries alive (rows carried into the next batch)."""
+        return 0 if self._carry is None else int(self._carry["kind"].shape[0])
+
+    def destroy(self):
+        if self._seen is not None:
+            self._seen.destroy()
+            self._seen = None
+        self._carry = None
