@@ -603,6 +603,130 @@ int igx_lw_join(igx_ctx *ctx, const uint64_t *key, const uint8_t *kind,
                 uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend);
 int igx_lw_join_tile(void);
 
+/* ---- the chained join through two maps ---------------------------------------------------- */
+/* The join that trace tcp (pkg/gadgets/trace/tcp/tracer/bpf/tcptracer.bpf.c) runs its connect
+ * events through: two hash maps one after the other, keyed by different things.  `sockets`
+ * (:59-64) is keyed by the thread: the tcp_v4/v6_connect kprobe writes it after filter_event
+ * (:182-185), the kretprobe looks it up and always deletes it (:203-205, :225).  `tuplepid`
+ * (:52-57) is keyed by the tuple: a kretprobe that found its `sockets` entry, returned 0 and could
+ * fill the tuple stores the connecting task there (:207-222); tcp_set_state, which runs in some
+ * other context and knows only the tuple, looks it up on TCP_ESTABLISHED and emits the connect
+ * event with what is stored (:314-324), and deletes the entry on TCP_ESTABLISHED and TCP_CLOSE
+ * (:326-327).  Whether a row writes the second map depends on what the first join found, and the
+ * gadget's filters reach the event only through the first map.
+ *
+ * A batch is nrows rows in stream order (row i before row i + 1): key1 (u64, the thread), key2
+ * (u64, an id of the tuple: equal tuples, equal ids), kind (u8, enum igx_cj_kind); rows with
+ * valid[i] == 0 (valid nullable) or any other kind do not exist for the join.  Every key of
+ * either map starts the batch with no entry.  In row order:
+ *   IGX_CJ_ENTER  map1[key1] := this row (overwrites; :185)
+ *   IGX_CJ_PASS   without map1[key1]: nothing (:203-205); else delete it and map2[key2] := this
+ *                 row (overwrites; :207-225 with ret == 0 and a complete tuple)
+ *   IGX_CJ_ABORT  delete map1[key1] if there is one, nothing else (:207-213 -> end)
+ *   IGX_CJ_TAKE   with map2[key2]: emit (this row, the row stored there); either way delete it
+ *                 (:314-327)
+ *   IGX_CJ_DROP   delete map2[key2]; emit nothing (TCP_CLOSE, :311-312, :327)
+ *   IGX_CJ_HELD   map2[key2] := this row, unconditionally: a PASS row that was admitted in an
+ *                 earlier batch and is carried in band (below)
+ * key1 matters for ENTER / PASS / ABORT rows only, key2 for PASS / HELD / TAKE / DROP rows only
+ * (both columns are read for every row, so every entry must be readable).
+ * take_row, pass_row (device, nrows entries each): entry j is the j-th emitting TAKE in stream
+ * order and the PASS or HELD row it found.  *d_ntake (device u64) is their number; entries at and
+ * past it are unspecified.  The rows still in a map at the end of the batch -- the ENTER rows in
+ * map 1 and the PASS / HELD rows in map 2 -- go to pend_row together, in stream order: nothing is
+ * written past pend_cap entries, and *d_npend (device u64) is their true number, which may exceed
+ * pend_cap.
+ *
+ * State crosses a batch boundary in band: put those rows, every column, in that order, in front
+ * of the next batch, and rewrite the kind of each carried PASS row to IGX_CJ_HELD -- its ENTER has
+ * been consumed, so as a PASS it would find map 1 empty and be dropped.  Carried ENTER and HELD
+ * rows keep their kind.  Any cut of one stream into batches then gives the emissions of the whole
+ * stream.  The maps' max_entries are not reproduced.
+ *
+ * How it reduces: two igx_lw_join pipelines over the same row index space.  Stage 1 on key1 with
+ * ENTER = SET_A, PASS / ABORT = TAKE_A; stage 2 on key2 with SET_A = a PASS that emitted in stage 1
+ * or a HELD row, TAKE_A = TAKE / DROP, and the emissions of DROP rows discarded (a delete is a take
+ * nobody reads).  The hand-over between them and the merge of the two pending lists are plain
+ * grids; the counts stay on the device.
+ *
+ * nrows <= 2^32 - 2 (IGX_EINVAL otherwise, checked before anything else is looked at); 0 is
+ * valid.  The keys and the counts are 8-byte aligned, the row outputs 4-byte aligned (IGX_EINVAL
+ * otherwise).  The outputs may not overlap the inputs or each other.  Work per row does not
+ * depend on how long a key's run is; beside the sort's, about 10 bytes per row of the context's
+ * scratch and 5 of its side arena (IGX_ENOMEM if they cannot be had, and nothing stays
+ * allocated).  Two host synchronisations (one digit plan per sort).  igx_chain_join_tile: the
+ * rows per tile of the device scans. */
+enum igx_cj_kind { IGX_CJ_ENTER = 0, IGX_CJ_PASS = 1, IGX_CJ_ABORT = 2,
+                   IGX_CJ_TAKE = 3, IGX_CJ_DROP = 4, IGX_CJ_HELD = 5 };
+int igx_chain_join(igx_ctx *ctx, const uint64_t *key1, const uint64_t *key2, const uint8_t *kind,
+                   const uint8_t *valid /*nullable*/, uint64_t nrows,
+                   uint32_t *take_row, uint32_t *pass_row, uint64_t *d_ntake,
+                   uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend);
+int igx_chain_join_tile(void);
+
+/* ---- trace tcp: what each probe decides per row -------------------------------------------- */
+/* One row per probe firing of tcptracer.bpf.c, with the fields the probe reads (device columns,
+ * nrows entries each): probe (u8, enum igx_tcp_probe), tid, pid, uid (u32), mntns (u64), ret (i32,
+ * connect-return), state (u8: the new state for set-state, the socket's skc_state for close),
+ * family (u16: skc_family; for connect-return the probe's own constant, :238, :250), netns (u32),
+ * saddr, daddr (16 bytes each; AF_INET uses the first 4), dport, sport (u16, as the socket holds
+ * them, i.e. network order), num (u16, skc_num, accept only).  filter_pid (0: none), filter_uid
+ * ((uint32_t)-1: none) and mntns_set (device, n_mntns <= 1024 ids sorted ascending; null: no
+ * mount-namespace filter, while a non-null set of 0 ids passes nothing) are the gadget's filter
+ * constants (:14-16, :72-77).
+ *
+ * Per row: kind[i], an igx_cj_kind or IGX_TCP_NO_KIND; event[i], 0 none, 1 accept, 2 close (the
+ * events a probe emits without a map); tuple + 40 * i, the tuple_key_t (:31-43: saddr 16, daddr
+ * 16, sport 2, dport 2, netns 4), written for PASS / TAKE / DROP rows and rows with an event and
+ * zero for all others; key1[i] = tid (key1 nullable).
+ *   fill_tuple (:79-122) reads netns, then saddr, daddr, dport, sport; the first zero among the
+ *     last four stops it and every later field stays zero.  AF_INET reads 4 bytes of each address
+ *     (the other 12 key bytes are zero whatever the column holds), AF_INET6 tests all 16 bytes,
+ *     any other family fails.
+ *   filter_event (:147-166) runs at connect-enter, close and accept only: family, then mount
+ *     namespace, then pid, then uid.
+ *   connect-enter   ENTER if filter_event passes.
+ *   connect-return  ABORT with ret != 0 or an incomplete tuple, else PASS.  No filter.
+ *   set-state       no filter.  A state other than ESTABLISHED (1) / CLOSE (7): nothing.  An
+ *                   incomplete tuple: nothing (its delete uses a key with a zero field, and no
+ *                   stored key has one).  CLOSE: DROP.  ESTABLISHED: TAKE.
+ *   close           (:253-294) old state SYN_SENT (2), SYN_RECV (3) or NEW_SYN_RECV (12): nothing;
+ *                   an incomplete tuple: nothing; else a close event.
+ *   accept          (:332-372) fill_tuple's result is ignored, then sport := bswap16(num), then
+ *                   nothing if saddr or daddr (as 128 bits), dport or sport is zero; else an
+ *                   accept event.  A socket whose inet_sport is zero but whose skc_num is not is
+ *                   reported.
+ * The return probe's socket fields are carried on the connect-return row (the reference reads
+ * them through the pointer its kprobe stored; csrc/k_tcptrace.h says when the two differ).
+ *
+ * nrows <= 2^32 - 2, n_mntns <= 1024; saddr / daddr 16-byte aligned, mntns, tuple, key1 and
+ * mntns_set 8-byte aligned, the other columns aligned to their width (IGX_EINVAL otherwise, and
+ * for a null context, before any pointer is read).  One launch, asynchronous, no scratch. */
+enum igx_tcp_probe { IGX_TCP_CONNECT_ENTER = 0, IGX_TCP_CONNECT_RETURN = 1, IGX_TCP_CLOSE = 2,
+                     IGX_TCP_SET_STATE = 3, IGX_TCP_ACCEPT_RETURN = 4 };
+#define IGX_TCP_NO_KIND 255
+#define IGX_TCP_TUPLE_BYTES 40
+typedef struct {
+    const uint8_t *probe;
+    const uint32_t *tid;
+    const uint32_t *pid;
+    const uint32_t *uid;
+    const uint64_t *mntns;
+    const int32_t *ret;
+    const uint8_t *state;
+    const uint16_t *family;
+    const uint32_t *netns;
+    const uint8_t *saddr;   /* n x 16 */
+    const uint8_t *daddr;   /* n x 16 */
+    const uint16_t *dport;
+    const uint16_t *sport;
+    const uint16_t *num;
+} igx_tcp_rows;
+int igx_tcp_classify(igx_ctx *ctx, const igx_tcp_rows *rows, uint64_t nrows,
+                     uint32_t filter_pid, uint32_t filter_uid,
+                     const uint64_t *mntns_set /*nullable*/, uint32_t n_mntns,
+                     uint8_t *tuple, uint8_t *kind, uint8_t *event, uint64_t *key1 /*nullable*/);
+
 /* ---- profile cpu: row interning, symbol lookup -------------------------------------------- */
 /* profile cpu (pkg/gadgets/profile/cpu/tracer/bpf/profile.bpf.c:60-114) keys its counts by
  * key_t (profile.h:9-16), whose two stack fields are ids: bpf_get_stackid (:93, :98) turns a

@@ -32,6 +32,10 @@ FILTER_ANY, FILTER_NIL_MATCH = 1, 2
 GB_AUTO, GB_CACHED, GB_DIRECT, GB_PART = 0, 1, 2, 3
 REQ_START, REQ_ISSUE, REQ_DONE = 0, 1, 2
 LW_SET_A, LW_SET_B, LW_CLEAR_B, LW_TAKE_A = 0, 1, 2, 3
+CJ_ENTER, CJ_PASS, CJ_ABORT, CJ_TAKE, CJ_DROP, CJ_HELD = 0, 1, 2, 3, 4, 5
+TCP_CONNECT_ENTER, TCP_CONNECT_RETURN, TCP_CLOSE, TCP_SET_STATE, TCP_ACCEPT_RETURN = 0, 1, 2, 3, 4
+TCP_NO_KIND, TCP_TUPLE_BYTES = 255, 40
+TCP_EV_NONE, TCP_EV_ACCEPT, TCP_EV_CLOSE = 0, 1, 2
 SECCOMP_SYSCALLS, SECCOMP_VALUE_BYTES = 500, 501
 
 
@@ -88,6 +92,12 @@ class OpenCols(C.Structure):
     """igx_open_cols: device outputs of igx_ingest_open_events (NULL = skipped)."""
     _fields_ = [(f, C.c_void_p) for f in ("timestamp", "pid", "uid", "mntns", "ret", "fd", "err",
                                            "comm", "path")]
+
+
+class TcpRows(C.Structure):
+    """igx_tcp_rows: the device columns of igx_tcp_classify's probe rows."""
+    _fields_ = [(f, C.c_void_p) for f in ("probe", "tid", "pid", "uid", "mntns", "ret", "state", "family", "netns",
+                                           "saddr", "daddr", "dport", "sport", "num")]
 
 
 OPEN_SAMPLE_BYTES = 304
@@ -170,6 +180,9 @@ SIGNATURES = [
     ("igx_req_join_tile", _I, []),
     ("igx_lw_join", _I, [_VP, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _VP, _VP, _U64, _VP]),
     ("igx_lw_join_tile", _I, []),
+    ("igx_chain_join", _I, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _VP, _U64, _VP]),
+    ("igx_chain_join_tile", _I, []),
+    ("igx_tcp_classify", _I, [_VP, C.POINTER(TcpRows), _U64, _U32, _U32, _VP, _U32, _VP, _VP, _VP, _VP]),
     ("igx_intern_create", _I, [_VP, _U32, _U64, C.POINTER(_VP)]),
     ("igx_intern_add", _I, [_VP, _VP, _U64, _VP, _U64, _VP]),
     ("igx_intern_add_first", _I, [_VP, _VP, _U64, _VP, _U64, _VP, _VP]),

@@ -146,6 +146,22 @@ int launch_sort_perm(igx_ctx *ctx, const SortPlanKey *keys, uint32_t nkeys, uint
                      uint32_t *out_perm, uint32_t limit, const uint32_t *rowmap,
                      uint32_t pos_stride = 8, const GoSortKey *gokeys = nullptr, uint32_t ngokeys = 0,
                      const uint64_t *d_nrows = nullptr, TopkHint *hint = nullptr);
+
+// k_lwjoin.hip's pipeline in two halves, for the joins composed of it (k_chainjoin.hip).  A row's
+// flag byte after lw_join_mark: LW_F_TAKE (an emitting TAKE_A), LW_F_LIVE (still in a register), 0.
+constexpr uint8_t LW_F_TAKE = 1, LW_F_LIVE = 2;
+struct LwWork {
+    uint8_t *flags;      // nrows bytes, scratch arena
+    uint2 *t_pair;       // per emitting TAKE_A row: (A row, B row or IGX_NO_COL)
+    uint32_t *perm;
+    uint32_t *cnt_t, *cnt_p;
+    uint64_t *off_t, *off_p;
+};
+int lw_join_mark(igx_ctx *ctx, const uint64_t *key, const uint8_t *kind, const uint8_t *valid, uint64_t nrows,
+                 uint32_t *perm, LwWork *w);
+int lw_join_emit(igx_ctx *ctx, const LwWork *w, uint64_t nrows, uint32_t *take_row, uint32_t *a_row,
+                 uint32_t *b_row, uint64_t *d_ntake, uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend);
+
 // data (device, n rows in the pre-sort order) sorted in place by Go 1.19 SliceStable, pass by pass
 int launch_go_stable(igx_ctx *ctx, const GoSortKey *keys, uint32_t nkeys, uint64_t nrows, const uint8_t *valid,
                      uint32_t *data);

@@ -19,7 +19,9 @@
 //   count / scan / compact   the flagged rows written out in stream order
 //
 // Every launch is a plain grid; no workgroup waits on another.  Algorithmic bytes per row:
-// DESIGN.md §4.
+// DESIGN.md §4.  The pipeline is callable in two halves (igx_internal.h: lw_join_mark through
+// apply, lw_join_emit from count on) for the joins composed of it (k_chainjoin.hip); igx_lw_join
+// is the two back to back.
 #include "k_common.h"
 #include "k_lwjoin.h"
 
@@ -35,7 +37,7 @@ constexpr int LW_TILE = TB * RPT;     // 2048 positions per scan tile
 constexpr int CRPT = 4;
 constexpr int CTILE = TB * CRPT;      // 1024 rows per compaction tile
 constexpr int CGROUPS = CTILE / 64;   // wave-row groups per compaction tile
-constexpr uint8_t F_TAKE = 1, F_LIVE = 2;
+constexpr uint8_t F_TAKE = LW_F_TAKE, F_LIVE = LW_F_LIVE;
 
 __device__ __forceinline__ LwSum lw_shfl_up(const LwSum &v, int o) {
     LwSum r;
@@ -272,6 +274,69 @@ __global__ __launch_bounds__(TB) void k_lw_compact(const uint8_t *__restrict__ f
 
 extern "C" int igx_lw_join_tile(void) { return LW_TILE; }
 
+// The pipeline through the apply pass: w->flags[r] says what row r ended as (LW_F_TAKE: an emitting
+// TAKE_A, with its A and B rows in w->t_pair[r]; LW_F_LIVE: still held in a register), all of it in
+// the scratch arena.  perm (nrows entries) holds the order and must outlive lw_join_emit.
+int lw_join_mark(igx_ctx *ctx, const uint64_t *key, const uint8_t *kind, const uint8_t *valid, uint64_t nrows,
+                 uint32_t *perm, LwWork *w) {
+    const uint64_t ntiles = (nrows + LW_TILE - 1) / LW_TILE, ctiles = (nrows + CTILE - 1) / CTILE;
+    const size_t code_b = igx_align(ntiles * LW_TILE, 256), flag_b = igx_align(nrows, 256);
+    const size_t pair_b = igx_align(nrows * 8, 256), sum_b = igx_align(ntiles * sizeof(LwSum), 256);
+    const size_t cnt_b = igx_align(ctiles * 4, 256), off_b = igx_align(ctiles * 8, 256);
+    const size_t need = code_b + flag_b + pair_b + 2 * sum_b + 2 * cnt_b + 2 * off_b;
+    void *s;
+    // ask before the sort, so that an arena that has to grow does it before the order exists
+    int rc = igx_scratch(ctx, need, &s);
+    if (rc) return rc;
+    SortPlanKey sk{};
+    sk.ptr = reinterpret_cast<const uint8_t *>(key);
+    sk.width = 8;
+    sk.kind = IGX_KIND_UINT;
+    sk.words = 2;
+    sk.stride = 8;
+    rc = launch_sort_perm(ctx, &sk, 1, nrows, nullptr, false, nullptr, perm, 0, nullptr);
+    if (rc) return rc;
+    rc = igx_scratch(ctx, need, &s);
+    if (rc) return rc;
+    char *c = reinterpret_cast<char *>(s);
+    uint8_t *code = reinterpret_cast<uint8_t *>(c);
+    uint8_t *flags = reinterpret_cast<uint8_t *>(c + code_b);
+    uint2 *t_pair = reinterpret_cast<uint2 *>(c + code_b + flag_b);
+    LwSum *sums = reinterpret_cast<LwSum *>(c + code_b + flag_b + pair_b);
+    LwSum *carry = reinterpret_cast<LwSum *>(c + code_b + flag_b + pair_b + sum_b);
+    char *q = c + code_b + flag_b + pair_b + 2 * sum_b;
+    w->flags = flags;
+    w->t_pair = t_pair;
+    w->perm = perm;
+    w->cnt_t = reinterpret_cast<uint32_t *>(q);
+    w->cnt_p = reinterpret_cast<uint32_t *>(q + cnt_b);
+    w->off_t = reinterpret_cast<uint64_t *>(q + 2 * cnt_b);
+    w->off_p = reinterpret_cast<uint64_t *>(q + 2 * cnt_b + off_b);
+
+    IGX_HIP(ctx, hipMemsetAsync(flags, 0, flag_b, ctx->stream));
+    hipLaunchKernelGGL(k_lw_code, dim3((unsigned)((nrows + TB - 1) / TB)), dim3(TB), 0, ctx->stream, key, kind, valid,
+                       perm, nrows, code);
+    hipLaunchKernelGGL(k_lw_summary, dim3((unsigned)ntiles), dim3(TB), 0, ctx->stream, code, nrows, sums);
+    hipLaunchKernelGGL(k_lw_carry, dim3(1), dim3(1024), 0, ctx->stream, sums, ntiles, carry);
+    hipLaunchKernelGGL(k_lw_apply, dim3((unsigned)ntiles), dim3(TB), 0, ctx->stream, code, perm, nrows, carry, flags,
+                       t_pair);
+    return IGX_OK;
+}
+
+// The flagged rows of w written out in stream order; b_row may be the perm that lw_join_mark used.
+int lw_join_emit(igx_ctx *ctx, const LwWork *w, uint64_t nrows, uint32_t *take_row, uint32_t *a_row,
+                 uint32_t *b_row, uint64_t *d_ntake, uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend) {
+    const uint64_t ctiles = (nrows + CTILE - 1) / CTILE;
+    hipLaunchKernelGGL(k_lw_count, dim3((unsigned)ctiles), dim3(TB), 0, ctx->stream, w->flags, nrows, w->cnt_t,
+                       w->cnt_p);
+    hipLaunchKernelGGL(k_lw_scan, dim3(2), dim3(1024), 0, ctx->stream, w->cnt_t, w->cnt_p, ctiles, w->off_t, w->off_p,
+                       d_ntake, d_npend);
+    hipLaunchKernelGGL(k_lw_compact, dim3((unsigned)ctiles), dim3(TB), 0, ctx->stream, w->flags, nrows, w->off_t,
+                       w->off_p, w->t_pair, take_row, a_row, b_row, pend_row, pend_cap);
+    IGX_HIP(ctx, hipGetLastError());
+    return IGX_OK;
+}
+
 extern "C" int igx_lw_join(igx_ctx *ctx, const uint64_t *key, const uint8_t *kind, const uint8_t *valid,
                            uint64_t nrows, uint32_t *take_row, uint32_t *a_row, uint32_t *b_row, uint64_t *d_ntake,
                            uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend) {
@@ -290,53 +355,11 @@ extern "C" int igx_lw_join(igx_ctx *ctx, const uint64_t *key, const uint8_t *kin
     if ((uintptr_t)key & 7) return igx_fail(ctx, IGX_EINVAL, "lw_join: key must be 8-byte aligned");
     if (((uintptr_t)take_row | (uintptr_t)a_row | (uintptr_t)b_row | (uintptr_t)pend_row) & 3)
         return igx_fail(ctx, IGX_EINVAL, "lw_join: row outputs must be 4-byte aligned");
-
-    const uint64_t ntiles = (nrows + LW_TILE - 1) / LW_TILE, ctiles = (nrows + CTILE - 1) / CTILE;
-    const size_t code_b = igx_align(ntiles * LW_TILE, 256), flag_b = igx_align(nrows, 256);
-    const size_t pair_b = igx_align(nrows * 8, 256), sum_b = igx_align(ntiles * sizeof(LwSum), 256);
-    const size_t cnt_b = igx_align(ctiles * 4, 256), off_b = igx_align(ctiles * 8, 256);
-    const size_t need = code_b + flag_b + pair_b + 2 * sum_b + 2 * cnt_b + 2 * off_b;
-    void *s;
-    // ask before the sort, so that an arena that has to grow does it before the order exists
-    int rc = igx_scratch(ctx, need, &s);
-    if (rc) return rc;
     // The order lives in b_row (read by the code and apply passes, written by the compaction,
     // which no longer needs it) while the scratch arena, which the sort uses too, is handed from
-    // the sort to the passes below.
-    uint32_t *perm = b_row;
-    SortPlanKey sk{};
-    sk.ptr = reinterpret_cast<const uint8_t *>(key);
-    sk.width = 8;
-    sk.kind = IGX_KIND_UINT;
-    sk.words = 2;
-    sk.stride = 8;
-    rc = launch_sort_perm(ctx, &sk, 1, nrows, nullptr, false, nullptr, perm, 0, nullptr);
+    // the sort to the passes.
+    LwWork w;
+    const int rc = lw_join_mark(ctx, key, kind, valid, nrows, b_row, &w);
     if (rc) return rc;
-    rc = igx_scratch(ctx, need, &s);
-    if (rc) return rc;
-    char *c = reinterpret_cast<char *>(s);
-    uint8_t *code = reinterpret_cast<uint8_t *>(c);
-    uint8_t *flags = reinterpret_cast<uint8_t *>(c + code_b);
-    uint2 *t_pair = reinterpret_cast<uint2 *>(c + code_b + flag_b);
-    LwSum *sums = reinterpret_cast<LwSum *>(c + code_b + flag_b + pair_b);
-    LwSum *carry = reinterpret_cast<LwSum *>(c + code_b + flag_b + pair_b + sum_b);
-    char *q = c + code_b + flag_b + pair_b + 2 * sum_b;
-    uint32_t *cnt_t = reinterpret_cast<uint32_t *>(q), *cnt_p = reinterpret_cast<uint32_t *>(q + cnt_b);
-    uint64_t *off_t = reinterpret_cast<uint64_t *>(q + 2 * cnt_b);
-    uint64_t *off_p = reinterpret_cast<uint64_t *>(q + 2 * cnt_b + off_b);
-
-    IGX_HIP(ctx, hipMemsetAsync(flags, 0, flag_b, ctx->stream));
-    hipLaunchKernelGGL(k_lw_code, dim3((unsigned)((nrows + TB - 1) / TB)), dim3(TB), 0, ctx->stream, key, kind, valid,
-                       perm, nrows, code);
-    hipLaunchKernelGGL(k_lw_summary, dim3((unsigned)ntiles), dim3(TB), 0, ctx->stream, code, nrows, sums);
-    hipLaunchKernelGGL(k_lw_carry, dim3(1), dim3(1024), 0, ctx->stream, sums, ntiles, carry);
-    hipLaunchKernelGGL(k_lw_apply, dim3((unsigned)ntiles), dim3(TB), 0, ctx->stream, code, perm, nrows, carry, flags,
-                       t_pair);
-    hipLaunchKernelGGL(k_lw_count, dim3((unsigned)ctiles), dim3(TB), 0, ctx->stream, flags, nrows, cnt_t, cnt_p);
-    hipLaunchKernelGGL(k_lw_scan, dim3(2), dim3(1024), 0, ctx->stream, cnt_t, cnt_p, ctiles, off_t, off_p, d_ntake,
-                       d_npend);
-    hipLaunchKernelGGL(k_lw_compact, dim3((unsigned)ctiles), dim3(TB), 0, ctx->stream, flags, nrows, off_t, off_p,
-                       t_pair, take_row, a_row, b_row, pend_row, pend_cap);
-    IGX_HIP(ctx, hipGetLastError());
-    return IGX_OK;
+    return lw_join_emit(ctx, &w, nrows, take_row, a_row, b_row, d_ntake, pend_row, pend_cap, d_npend);
 }

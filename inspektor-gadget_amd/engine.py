@@ -595,6 +595,85 @@ def lw_join(key, kind, valid=None, pend_cap=None, sync=True):
 
 
 # ------------------------------------------------------------------------------------
+# the chained join through two maps, and trace tcp's per-row rules
+# ------------------------------------------------------------------------------------
+def chain_join_tile():
+    """igx_chain_join_tile: rows per tile of the join's device scans (host call, no GPU)."""
+    return int(_abi.lib().igx_chain_join_tile())
+
+
+def chain_join(key1, key2, kind, valid=None, pend_cap=None, sync=True):
+    """igx_chain_join: the join through two chained maps (tcptracer.bpf.c:52-64, :168-227,
+    :296-330; the contract is in include/igx.h).  key1, key2: u64 (or int64) device tensors, kind
+    (_abi.CJ_*) and valid: uint8, all of n rows in stream order.
+    Returns a dict: take, pass (int32 row ids), one entry per emitting TAKE in stream order; pend,
+    the ENTER / PASS / HELD rows still in a map at the end, in stream order (at most pend_cap of
+    them, default n); n_take and n_pend, the true counts.  sync=True reads the counts (one host
+    read) and trims the tensors; sync=False returns full-capacity tensors and the counts as
+    device u64 tensors."""
+    torch = torch_mod()
+    ctx = context()
+    n = int(key1.numel())
+    if int(key2.numel()) != n or int(kind.numel()) != n:
+        raise ValueError("chain_join: key1, key2 and kind must have the same number of rows")
+    cap = n if pend_cap is None else int(pend_cap)
+    dev = key1.device
+    key1, key2, kind = key1.contiguous(), key2.contiguous(), kind.contiguous()
+    valid = None if valid is None else valid.contiguous()
+    m = max(1, n)
+    take_, pass_ = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(2))
+    pend = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
+    cnt = torch.empty(2, dtype=torch.uint64, device=dev)
+    ctx.check(ctx.L.igx_chain_join(ctx.h, ptr(key1), ptr(key2), ptr(kind), ptr(valid), n, ptr(take_), ptr(pass_),
+                                   C.c_void_p(cnt.data_ptr()), ptr(pend), cap, C.c_void_p(cnt.data_ptr() + 8)))
+    out = {"take": take_[:n], "pass": pass_[:n], "pend": pend[:cap], "n_take": cnt[0:1], "n_pend": cnt[1:2]}
+    if not sync:
+        return out
+    nt, npend = (int(x) for x in cnt.cpu().view(torch.int64))
+    for k in ("take", "pass"):
+        out[k] = out[k][:nt]
+    out["pend"] = out["pend"][:min(npend, cap)]
+    out["n_take"], out["n_pend"] = nt, npend
+    return out
+
+
+TCP_ROW_FIELDS = ("probe", "tid", "pid", "uid", "mntns", "ret", "state", "family", "netns", "saddr", "daddr",
+                  "dport", "sport", "num")
+_TCP_ROW_BYTES = {"probe": 1, "tid": 4, "pid": 4, "uid": 4, "mntns": 8, "ret": 4, "state": 1, "family": 2,
+                  "netns": 4, "saddr": 16, "daddr": 16, "dport": 2, "sport": 2, "num": 2}
+
+
+def tcp_classify(rows, filter_pid=0, filter_uid=-1, mntns_set=None):
+    """igx_tcp_classify: what each probe of trace tcp decides per row (tcptracer.bpf.c:79-166 and
+    the probes; the contract is in include/igx.h).  rows: a dict of device tensors named as
+    TCP_ROW_FIELDS (saddr / daddr are (n, 16) uint8; the others 1-D of their width).  mntns_set:
+    None (no mount-namespace filter) or a device u64 tensor of up to 1024 ids sorted ascending.
+    Returns a dict: tuple (uint8 (n, 40)), kind (uint8, _abi.CJ_* or _abi.TCP_NO_KIND), event
+    (uint8, _abi.TCP_EV_*), key1 (int64, the thread).  Asynchronous."""
+    torch = torch_mod()
+    ctx = context()
+    n = int(rows["probe"].numel())
+    cols = {}
+    for f in TCP_ROW_FIELDS:
+        t = rows[f].contiguous()
+        if t.numel() * t.element_size() != n * _TCP_ROW_BYTES[f]:
+            raise ValueError(f"tcp_classify: column {f} must hold {_TCP_ROW_BYTES[f]} bytes per row")
+        cols[f] = t
+    dev = cols["probe"].device
+    m = max(1, n)
+    tup = torch.empty((m, _abi.TCP_TUPLE_BYTES // 8), dtype=torch.int64, device=dev).view(torch.uint8)
+    kind, event = (torch.empty(m, dtype=torch.uint8, device=dev) for _ in range(2))
+    key1 = torch.empty(m, dtype=torch.int64, device=dev)
+    st = _abi.TcpRows(*[ptr(cols[f]) for f in TCP_ROW_FIELDS])
+    ns = None if mntns_set is None else mntns_set.contiguous()
+    ctx.check(ctx.L.igx_tcp_classify(ctx.h, C.byref(st), n, int(filter_pid) & 0xFFFFFFFF,
+                                     int(filter_uid) & 0xFFFFFFFF, None if ns is None else C.c_void_p(ns.data_ptr()),
+                                     0 if ns is None else int(ns.numel()), ptr(tup), ptr(kind), ptr(event),
+                                     ptr(key1)))
+    return {"tuple": tup[:n], "kind": kind[:n], "event": event[:n], "key1": key1[:n]}
+
+
+# ------------------------------------------------------------------------------------
 # traceloop: the enter / exit / cont join by timestamp
 # ------------------------------------------------------------------------------------
 TRACELOOP_NR_X86_64 = (60, 231, 15)    # exit, exit_group, rt_sigreturn (traceloop.bpf.c:12-35)

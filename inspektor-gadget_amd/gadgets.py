@@ -1,6 +1,6 @@
 """The aggregation gadgets as their tracers expose them: top tcp / file / block-io,
-profile block-io / cpu, advise seccomp-profile, traceloop and trace capabilities, on top of
-libigx.so.
+profile block-io / cpu, advise seccomp-profile, traceloop, trace capabilities and trace tcp, on
+top of libigx.so.
 
 Each `Top*` class is the user-space half of a reference tracer plus the BPF map update it
 drains, re-cut for batches of events resident in HBM:
@@ -26,6 +26,8 @@ References (paths under the reference root):
                 types/types.go:27-56
   trace capabilities  pkg/gadgets/trace/capabilities/tracer/bpf/capable.bpf.c:87-248,
                 tracer/tracer.go:224-318, types/types.go:35-73
+  trace tcp     pkg/gadgets/trace/tcp/tracer/bpf/tcptracer.bpf.c:79-372, tracer/tracer.go:198-234,
+                types/types.go:22-55
 
 The reference's pre-sort order (BPF hash iteration) is replaced by each group's first
 event index; everything else -- keys, wrap widths, sort order including
@@ -1819,4 +1821,186 @@ class TraceCapabilitiesTracer:
         if self._seen is not None:
             self._seen.destroy()
             self._seen = None
+        self._carry = None
+
+
+# ------------------------------------------------------------------------------------
+# trace tcp: pkg/gadgets/trace/tcp (tracer/bpf/tcptracer.bpf.c, tracer/tracer.go:198-234,
+# types/types.go:22-55)
+# ------------------------------------------------------------------------------------
+TCP_TRACE_COLS = engine.TCP_ROW_FIELDS + ("ts", "comm")
+_TCP_OPERATIONS = {_abi.TCP_EV_ACCEPT: "accept", _abi.TCP_EV_CLOSE: "close", 3: "connect"}
+
+
+def Htons(hs: int) -> int:
+    """helpers.go:105-109 on a little-endian host: the two bytes of a uint16 swapped."""
+    hs = int(hs) & 0xFFFF
+    return ((hs & 0xFF) << 8) | (hs >> 8)
+
+
+@dataclass
+class TcpEvent:
+    """pkg/gadgets/trace/tcp/types/types.go:22-34 (eventtypes.Event + WithMountNsID flattened)."""
+    Node: str = ""
+    Namespace: str = ""
+    Pod: str = ""
+    Container: str = ""
+    Timestamp: int = 0
+    Type: str = "normal"
+    MountNsID: int = 0
+    Operation: str = ""
+    Pid: int = 0
+    Comm: str = ""
+    IPVersion: int = 0
+    Saddr: str = ""
+    Daddr: str = ""
+    Sport: int = 0
+    Dport: int = 0
+
+
+_TCP_EVENT_JSON = _COMMON_JSON[:4] + [("Timestamp", "timestamp", True), ("Type", "type", False),
+                                      ("MountNsID", "mountnsid", True), ("Operation", "operation", True),
+                                      ("Pid", "pid", True), ("Comm", "comm", True), ("IPVersion", "ipversion", True),
+                                      ("Saddr", "saddr", True), ("Daddr", "daddr", True), ("Sport", "sport", True),
+                                      ("Dport", "dport", True)]
+
+
+def tcp_event(op, family, tuple40, pid, mntns, comm, ts, boot_to_wall_ns=0) -> TcpEvent:
+    """tracer.go:198-228 for one event of the probes: op is the event type (1 accept, 2 close,
+    3 connect), tuple40 the tuple_key_t bytes the probe filled the event from (fill_event,
+    tcptracer.bpf.c:124-144)."""
+    t = bytes(tuple40)
+    v = 4 if int(family) == AF_INET else 6 if int(family) == AF_INET6 else 0
+    return TcpEvent(Timestamp=int(ts) + boot_to_wall_ns, MountNsID=int(mntns), Operation=_TCP_OPERATIONS.get(int(op), ""),
+                    Pid=int(pid), Comm=FromCString(comm), IPVersion=v, Saddr=IPStringFromBytes(t[0:16], v),
+                    Daddr=IPStringFromBytes(t[16:32], v), Sport=Htons(int.from_bytes(t[32:34], "little")),
+                    Dport=Htons(int.from_bytes(t[34:36], "little")))
+
+
+def tcp_event_json(ev: TcpEvent) -> str:
+    """json.Marshal of one event (the struct tags of types.go:22-34 and pkg/types/types.go)."""
+    from . import textcolumns as T
+    return T.marshal(ev, _TCP_EVENT_JSON)
+
+
+def TraceTcpColumns():
+    """types.GetColumns() (types.go:36-55): the `t` extractor maps the operation to A / C / X / U."""
+    from . import textcolumns as T
+    cm = T.ColumnMap([(a, k, t) for a, k, t, _ in _COMMON_COLS[:4]] +
+                     [("Timestamp", "int64", "timestamp,template:timestamp"), ("MountNsID", "uint64", "mntns,template:ns"),
+                      ("Operation", "string", "t,width:1,fixed"), ("Pid", "uint32", "pid,template:pid"),
+                      ("Comm", "string", "comm,template:comm"), ("IPVersion", "int", "ip,width:2,fixed"),
+                      ("Saddr", "string", "saddr,template:ipaddr"), ("Daddr", "string", "daddr,template:ipaddr"),
+                      ("Sport", "uint16", "sport,template:ipport"), ("Dport", "uint16", "dport,template:ipport")])
+    for a, _, t, tags in _COMMON_COLS[:4]:
+        cm.cols[t.split(",")[0]].Tags = list(tags)
+    cm.SetExtractor("t", lambda ev: {"accept": "A", "connect": "C", "close": "X", "unknown": "U"}.get(ev.Operation, "U"))
+    for name in ("node", "namespace", "pod", "container"):
+        cm.cols[name].Visible = False
+    return cm
+
+
+def tcp_render(events, terminal_width: int = 0, columns=None) -> str:
+    """The columns output of a list of events."""
+    from . import textcolumns as T
+    return T.TransformIntoTable(T.TextColumnsFormatter(TraceTcpColumns(), DefaultColumns=columns), events,
+                                terminal_width)
+
+
+class TraceTcpTracer:
+    """trace tcp from its probes' own rows (tcptracer.bpf.c), on the device: igx_tcp_classify
+    applies fill_tuple and filter_event per row, the connect events run through igx_chain_join
+    (`sockets` keyed by the thread, then `tuplepid` keyed by the tuple), accept and close events
+    are per-row filters.
+
+    feed(batch) takes device columns (TCP_TRACE_COLS) of probe rows in stream order: probe (uint8,
+    _abi.TCP_*), tid, pid, uid (u32), mntns (u64), ret (i32), state (u8), family (u16), netns (u32),
+    saddr, daddr ((n, 16) u8), dport, sport, num (u16, as the socket holds them), ts (u64, boot ns),
+    comm ((n, 16) u8).  It returns the events in the order of the rows that emit them (perf-ring
+    order).  A connect event has the tuple, family and timestamp of the tcp_set_state row and the
+    pid / mntns / comm of the connect-return row (:319-321).  Rows still in a map after a batch are
+    carried into the next one -- an admitted connect-return as IGX_CJ_HELD -- and meet no filter
+    again; more than pending_cap of them raises IgxError(IGX_ENOSPC).
+
+    The tuples become igx_chain_join's key2 through a fresh engine.Interner(40) per batch: carried
+    rows are fed again in front, so ids need not outlive a batch.  mntns_filter: an iterable of up
+    to 1024 mount namespace ids, or None.  filter_pid 0 and filter_uid -1 are "none", as the BPF
+    constants.  boot_to_wall_ns: WallTimeFromBootTime's offset."""
+
+    _CARRIED = TCP_TRACE_COLS + ("_kind", "_tuple", "_key1")
+
+    def __init__(self, mntns_filter=None, filter_pid=0, filter_uid=-1, pending_cap=1 << 20, boot_to_wall_ns=0):
+        self.mntns_filter = None if mntns_filter is None else sorted(set(int(x) for x in mntns_filter))
+        if self.mntns_filter is not None and len(self.mntns_filter) > 1024:
+            raise ValueError("trace tcp: the mount namespace filter holds at most 1024 ids")
+        self.filter_pid, self.filter_uid = int(filter_pid), int(filter_uid)
+        self.pending_cap, self.boot_to_wall_ns = int(pending_cap), int(boot_to_wall_ns)
+        self._carry = None            # {column: tensor} of the rows still in `sockets` / `tuplepid`
+        self._ns = None
+
+    def _classify(self, c):
+        torch = torch_mod()
+        dev = c["probe"].device
+        if self.mntns_filter is not None and len(self.mntns_filter) == 0:
+            # an empty tensor has no address to pass, and igx_tcp_classify reads a null set as "no filter"
+            raise ValueError("trace tcp: an empty mount namespace filter passes nothing; pass None for no filter")
+        if self.mntns_filter is not None and (self._ns is None or self._ns.device != dev):
+            import numpy as np
+            self._ns = torch.from_numpy(np.array(self.mntns_filter, np.uint64).view(np.int64)).to(dev)
+        return engine.tcp_classify(c, self.filter_pid, self.filter_uid, self._ns)
+
+    def feed(self, batch: dict, n: Optional[int] = None) -> List[TcpEvent]:
+        torch = torch_mod()
+        n = int(batch["probe"].shape[0]) if n is None else n
+        c = {k: batch[k][:n] for k in TCP_TRACE_COLS}
+        cl = self._classify(c)
+        c["_kind"], c["_tuple"], c["_key1"], event = cl["kind"], cl["tuple"], cl["key1"], cl["event"]
+        if self._carry is not None:
+            # the carried rows were admitted when they came: no filter again, and their own events are out
+            event = torch.cat([torch.zeros(self._carry["_kind"].shape[0], dtype=torch.uint8, device=event.device), event])
+            c = {k: _cat_rows(self._carry[k], v) for k, v in c.items()}
+        total = int(c["_kind"].shape[0])
+        if total == 0:
+            return []
+        kind = c["_kind"]
+        keyed = ((kind == _abi.CJ_PASS) | (kind == _abi.CJ_HELD) | (kind == _abi.CJ_TAKE) | (kind == _abi.CJ_DROP))
+        interner = engine.Interner(_abi.TCP_TUPLE_BYTES, total)
+        try:
+            key2 = interner.add(c["_tuple"], keyed.to(torch.uint8)).to(torch.int64)
+            j = engine.chain_join(c["_key1"], key2, kind, pend_cap=self.pending_cap)
+        finally:
+            interner.destroy()
+        if j["n_pend"] > self.pending_cap:
+            raise _abi.IgxError(_abi.IGX_ENOSPC, f"trace tcp: {j['n_pend']} map entries exceed "
+                                                 f"pending_cap={self.pending_cap}")
+        if j["n_pend"]:
+            names = list(c)
+            carry = dict(zip(names, engine.take([c[k] for k in names], j["pend"])))
+            carry["_kind"] = torch.where(carry["_kind"] == _abi.CJ_PASS, torch.full_like(carry["_kind"], _abi.CJ_HELD),
+                                         carry["_kind"])
+            self._carry = carry
+        else:
+            self._carry = None
+        # one op per emitting row, and the row its task fields come from; nonzero() keeps row order
+        op = event.clone()
+        src = torch.arange(total, dtype=torch.int32, device=op.device)
+        if j["n_take"]:
+            t64 = j["take"].to(torch.int64)
+            op[t64] = 3
+            src[t64] = j["pass"]
+        rows = torch.nonzero(op).flatten().to(torch.int32)
+        if rows.numel() == 0:
+            return []
+        ops, tup, fam, ts = engine.take([op, c["_tuple"], c["family"], c["ts"]], rows)
+        pid, mntns, comm = engine.take([c["pid"], c["mntns"], c["comm"]], src[rows.to(torch.int64)])
+        h = [host(t) for t in (ops, fam, tup, pid, mntns, comm, ts)]
+        return [tcp_event(h[0][i], h[1][i], h[2][i].tobytes(), h[3][i], h[4][i], h[5][i].tobytes(), h[6][i],
+                          self.boot_to_wall_ns) for i in range(len(h[0]))]
+
+    @property
+    def pending(self):
+        """Map entries alive (rows carried into the next batch)."""
+        return 0 if self._carry is None else int(self._carry["_kind"].shape[0])
+
+    def destroy(self):
         self._carry = None
