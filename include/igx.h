@@ -384,6 +384,19 @@ typedef struct {
     uint64_t gen_keys;   /* ... keys the table's generation held after it (UINT64_MAX: it ended) */
 } igx_groupby_info_t;
 int igx_groupby_info(igx_table *t, igx_groupby_info_t *out);
+/* The update log: a cached update of a table that is not wide, has 1-4 aggregates
+ * and at most 128 MiB of (slot, aggregate) sums streams the sums of the rows that miss the LDS
+ * cache to a log and adds them per slot bucket in LDS, instead of one atomic each.  Counters of
+ * the last collected finalize's interval (they ride its read-back): records logged, and updates
+ * that went out as atomics instead because their value was 2^32 or more, their workgroup's log
+ * region was full, or their bucket's region was full.  All 0: the interval did not log. */
+typedef struct {
+    uint64_t logged;
+    uint64_t fallback_value;
+    uint64_t fallback_log_full;
+    uint64_t fallback_bucket_full;
+} igx_groupby_log_stats_t;
+int igx_groupby_log_stats(igx_table *t, igx_groupby_log_stats_t *out);
 /* Row plans: a cached update whose shape -- key layout, aggregates, fused
  * predicates, no valid mask, no index column, no divisor -- is exactly the one a shipped gadget
  * builds runs a kernel instance compiled for that shape; any other update, and every update under

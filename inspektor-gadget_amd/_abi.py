@@ -66,6 +66,11 @@ class GroupbyInfo(C.Structure):
                 ("claims", C.c_uint64), ("gen_keys", C.c_uint64)]
 
 
+class GroupbyLogStats(C.Structure):
+    _fields_ = [("logged", C.c_uint64), ("fallback_value", C.c_uint64),
+                ("fallback_log_full", C.c_uint64), ("fallback_bucket_full", C.c_uint64)]
+
+
 class Agg(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("col", C.c_uint32), ("cond_col", C.c_uint32),
                 ("out_width", C.c_uint32), ("cond_val", C.c_uint64), ("divisor", C.c_uint64)]
@@ -158,6 +163,7 @@ SIGNATURES = [
     ("igx_groupby_finalize_async", _I, [_VP, C.POINTER(TableView)]),
     ("igx_groupby_wait", _I, [_VP, C.POINTER(C.c_uint64)]),
     ("igx_groupby_info", _I, [_VP, C.POINTER(GroupbyInfo)]),
+    ("igx_groupby_log_stats", _I, [_VP, C.POINTER(GroupbyLogStats)]),
     ("igx_groupby_rowplan", _I, [_VP]),
     ("igx_groupby_rowplan_match", _I, [C.POINTER(_U32), _U32, C.POINTER(Agg), _U32, C.POINTER(Col), _U32,
                                        C.POINTER(_U32), C.POINTER(Pred), _U32, _VP, _U32]),

@@ -279,6 +279,14 @@ template <bool DBG>
 __device__ __forceinline__ void ring_serve(const GbArgs &a, const Ring &r, uint32_t lane) {
     uint32_t head = 0;
     [[maybe_unused]] uint32_t prev_last = 0xFFFFFFFFu;   // diagnostics: the last record of the previous instruction
+    // The update log (k_gb_log.hip): a batch's sums leave as one contiguous wave store of 8-byte
+    // records into this workgroup's region instead of as atomics.  This wave is the region's only
+    // writer, so lpos is its cursor.  A minimum, a value of 2^32 or more, a slot the record cannot
+    // hold and every entry of a batch the region has no room for go out as atomics as before; in a
+    // logged batch such an entry's position holds a null record, so positions stay dense.
+    const bool logging = !DBG && a.log != nullptr;
+    uint64_t *lg = a.log + (uint64_t)blockIdx.x * a.log_cap;
+    uint32_t lpos = 0, n_logged = 0, n_value = 0, n_full = 0;
     for (;;) {
         const uint32_t t = __hip_atomic_load(&r.ctl[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (t == head) {
@@ -290,6 +298,7 @@ __device__ __forceinline__ void ring_serve(const GbArgs &a, const Ring &r, uint3
             continue;                      // they bound their own waits)
         }
         const uint32_t n = min(t - head, 64u);
+        const bool room = logging && lpos + n <= a.log_cap;
         uint32_t slot = 0xFFFFFFFFu, what = 0;
         if (lane < n) {
             const uint32_t p = head + lane;
@@ -304,12 +313,28 @@ __device__ __forceinline__ void ring_serve(const GbArgs &a, const Ring &r, uint3
             const uint64_t val = r.hi[p % ARING];
             slot = (uint32_t)w;
             what = (uint32_t)(w >> 32) & 15u;
-            if (DBG && (a.dbg & 131072u)) {   // diagnostics: plain stores instead of the atomics
+            bool logged = false;
+            if (logging && what != WHAT_MIN) {
+                const bool small = (val >> 32) == 0;
+                const bool fits = small && slot < LOG_SLOT_LIMIT;
+                if (!small) ++n_value;
+                if (fits && !room) ++n_full;
+                logged = fits && room;
+                n_logged += logged ? 1u : 0u;
+            }
+            if (room)
+                __builtin_nontemporal_store(logged ? log_record(slot, what, (uint32_t)val) : ~0ull, lg + lpos + lane);
+            if (logged) {   // the reduce pass adds it
+            } else if (DBG && (a.dbg & 131072u)) {   // diagnostics: plain stores instead of the atomics
                 if (what == WHAT_MIN) *rec_first(a, slot) = val;
                 else *rec_agg(a, slot, (int)what) = val;
             } else if (!(DBG && (a.dbg & 4u))) {
                 if (what == WHAT_MIN) gmin(rec_first(a, slot), val);
+#ifndef IGX_DIAG_NO_SERVER_ADDS   // diagnostic build only (wrong sums): what the server's adds cost
                 else gadd(rec_agg(a, slot, (int)what), val);
+#else
+                else asm volatile("" ::"v"(val));   // the ring read stays
+#endif
             }
         }
         if (DBG && (a.dbg & 262144u)) {
@@ -334,7 +359,22 @@ __device__ __forceinline__ void ring_serve(const GbArgs &a, const Ring &r, uint3
             prev_last = last_slot;
         }
         head += n;
+        if (room) lpos += n;
         if (lane == 0) __hip_atomic_store(&r.ctl[1], head, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    if (logging) {
+        for (int o = 32; o > 0; o >>= 1) {
+            n_logged += __shfl_xor(n_logged, o);
+            n_value += __shfl_xor(n_value, o);
+            n_full += __shfl_xor(n_full, o);
+        }
+        if (lane == 0) {
+            a.log_cnt[blockIdx.x] = lpos;
+            unsigned long long *st = reinterpret_cast<unsigned long long *>(a.err) + LOG_STAT_WORD;
+            if (n_logged) atomicAdd(st, (unsigned long long)n_logged);
+            if (n_value) atomicAdd(st + 1, (unsigned long long)n_value);
+            if (n_full) atomicAdd(st + 2, (unsigned long long)n_full);
+        }
     }
 }
 
@@ -1263,6 +1303,7 @@ int seeds_compute_static(igx_table *t, igx_ctx *ctx, const GbArgs &a) {
     b.seeds = nullptr;
     b.seed_gep = nullptr;
     b.nseeds = 0;
+    b.log = nullptr;
     st->rows_fed = S;
     st->fin_since_update = false;
     st->interval_direct = st->interval_part = false;

@@ -190,7 +190,23 @@ struct GbArgs {
     const uint32_t *seeds;
     const uint64_t *seed_gep;
     uint32_t nseeds;
+    // update log (cached form with the server wave; k_gb_log.hip): null = every update goes out as
+    // an atomic.  Workgroup w's server wave writes 8-byte records {value, (slot << 2) | aggregate}
+    // at log + w * log_cap and its record count (nulls included) to log_cnt[w].
+    uint32_t log_cap;
+    uint64_t *log;
+    uint32_t *log_cnt;
 };
+
+// ---- the update log's records and counters (k_gb_cached.hip writes, k_gb_log.hip reads) ----
+constexpr uint32_t LOG_NULL_HI = 0xFFFFFFFFu;          // a position whose entry went out as an atomic
+constexpr uint32_t LOG_SLOT_LIMIT = (1u << 30) - 1;    // slots below it fit a record
+// u64 words of the error block (igx_table::err) counted per interval: records logged, and the
+// entries that fell back to atomics because of their value, a full log region, a full bucket region
+constexpr int LOG_STAT_WORD = 8;
+__device__ __forceinline__ uint64_t log_record(uint32_t slot, uint32_t agg, uint32_t value) {
+    return ((uint64_t)((slot << 2) | agg) << 32) | value;
+}
 
 // Key hash: NH (the UMAC inner hash) over the key's word pairs -- one 32x32->64 multiply
 // per 8 key bytes, sum(( k[2i] + K[2i]) * (k[2i+1] + K[2i+1])) mod 2^64 -- then the murmur3
@@ -925,6 +941,14 @@ struct igx_table {
     size_t p_cnt_bytes = 0;
     uint8_t *p_mask = nullptr;   // row mask of the predicates that are not fused (grow-only)
     size_t p_mask_bytes = 0;
+    // update log scratch (k_gb_log.hip; first use, grow-only): the workgroups' log regions, the
+    // bucket regions, and the counters (one per workgroup, then one per bucket)
+    uint64_t *lg_recs = nullptr;
+    size_t lg_recs_bytes = 0;
+    uint64_t *lg_bk = nullptr;
+    size_t lg_bk_bytes = 0;
+    uint32_t *lg_cnt = nullptr;
+    uint64_t log_last[4] = {};   // the last collected finalize's log counters (igx_groupby_log_stats)
     uint64_t host_groups = 0;
     uint64_t *fin_host = nullptr;   // pinned, coherent: error word, LDS misses, group count (finalize read-back)
     uint64_t *fin_dev = nullptr;    // the same buffer as the kernels address it
@@ -1051,6 +1075,11 @@ inline int grow(igx_ctx *ctx, void **p, size_t *have, size_t need) {
 int gb_launch_cached(igx_table *t, GbArgs &a, uint32_t blocks);
 int gb_launch_estimate(igx_table *t, const GbArgs &a, uint32_t blocks, uint64_t nsample);
 int gb_seeds_compute(igx_table *t, const GbArgs &a);
+// k_gb_log.hip: the update log of a cached update over `blocks` workgroups.  gb_log_prepare
+// decides whether the update logs (0: it does not) and then allocates the scratch and points the
+// arguments at it; gb_log_launch, after the cached kernel, runs the partition and reduce passes.
+int gb_log_prepare(igx_table *t, GbArgs &a, uint32_t blocks);
+int gb_log_launch(igx_table *t, const GbArgs &a, uint32_t blocks);
 // k_gb_direct.hip
 int gb_launch_direct(igx_table *t, GbArgs &a);
 // k_gb_part.hip: passes K, O, S, A, B and the plan, then pass C (k_gb_part_c.hip)

@@ -99,6 +99,10 @@ __device__ __forceinline__ void fin_export(const uint32_t *err, uint64_t total, 
     __hip_atomic_store(host + 2, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(host + 4, claims, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(host + 5, keys, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (int x = 0; x < 4; ++x)   // the update log's counters ride the same read-back
+        __hip_atomic_store(host + LOG_STAT_WORD + x,
+                           *(reinterpret_cast<const volatile uint64_t *>(err) + LOG_STAT_WORD + x), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
     __threadfence_system();
     __hip_atomic_store(host + 3, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -207,6 +211,7 @@ __global__ __launch_bounds__(256) void k_reset_clear(uint32_t *__restrict__ occ,
     for (uint64_t q = i; q < nb16; q += stride) occb[q] = make_uint4(0, 0, 0, 0);
     if (i < (nwords & 3)) occ[n4 * 4 + i] = 0;
     if (i < 4) err[i] = 0;
+    if (i >= 2 * LOG_STAT_WORD && i < 2 * LOG_STAT_WORD + 8) err[i] = 0;   // the update log's counters
     const bool cont = rg.may && rg.gen[1] <= rg.limit;
     if (cont) {
         // one lane per 16-B quad of a record, a record's quads in adjacent lanes: each record
@@ -444,8 +449,8 @@ extern "C" int igx_groupby_create(igx_ctx *ctx, const uint32_t *key_widths, uint
     hipError_t e = hipMalloc(&t->krec, ns * t->krec_len);
     if (e == hipSuccess) e = hipMemsetAsync(t->krec, 0, ns * t->krec_len, ctx->stream);
     if (e == hipSuccess) e = hipMalloc(&t->vrec, ns * t->vrec_len);
-    if (e == hipSuccess) e = hipMalloc(&t->err, 64);
-    if (e == hipSuccess) e = hipMemsetAsync(t->err, 0, 64, ctx->stream);
+    if (e == hipSuccess) e = hipMalloc(&t->err, 128);   // error block, generation block, count, log counters
+    if (e == hipSuccess) e = hipMemsetAsync(t->err, 0, 128, ctx->stream);
     if (e == hipSuccess) e = hipMalloc(&t->groups, ns * 4);
     if (e == hipSuccess) e = hipMalloc(&t->tile_cnt, tiles * 4);
     t->occ_words = (ns + 31) / 32;
@@ -455,9 +460,9 @@ extern "C" int igx_groupby_create(igx_ctx *ctx, const uint32_t *key_widths, uint
     if (e == hipSuccess) t->n_groups = reinterpret_cast<uint64_t *>(t->err + 4);   // behind the error block
     if (e == hipSuccess) e = hipMalloc(&t->dbg_cnt, 256);
     if (e == hipSuccess)
-        e = hipHostMalloc(reinterpret_cast<void **>(&t->fin_host), 64, hipHostMallocMapped | hipHostMallocCoherent);
+        e = hipHostMalloc(reinterpret_cast<void **>(&t->fin_host), 128, hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&t->fin_dev), t->fin_host, 0);
-    if (e == hipSuccess) std::fill(t->fin_host, t->fin_host + 8, 0ull);
+    if (e == hipSuccess) std::fill(t->fin_host, t->fin_host + 16, 0ull);
     if (e == hipSuccess) e = hipMemsetAsync(t->dbg_cnt, 0, 256, ctx->stream);
     if (e != hipSuccess) {
         igx_groupby_destroy(t);
@@ -554,6 +559,9 @@ extern "C" int igx_groupby_destroy(igx_table *t) {
     (void)hipFree(t->p_recs);
     (void)hipFree(t->p_cnt);
     (void)hipFree(t->p_mask);
+    (void)hipFree(t->lg_recs);
+    (void)hipFree(t->lg_bk);
+    (void)hipFree(t->lg_cnt);
     for (auto &h : t->tk) (void)hipFree(h.slots);
     (void)hipFree(t->tk_state);
     for (auto *p : t->text) (void)hipFree(p);
@@ -632,7 +640,11 @@ static int launch_form(igx_table *t, GbArgs &a) {
         a.seed_gep = t->seed_gep;
         a.nseeds = t->nseeds;
     }
-    return gb_launch_cached(t, a, blocks);
+    // the update log: the server waves stream the misses' sums, two passes add them (k_gb_log.hip)
+    int rc = gb_log_prepare(t, a, blocks);
+    if (rc) return rc;
+    if ((rc = gb_launch_cached(t, a, blocks))) return rc;
+    return gb_log_launch(t, a, blocks);
 }
 
 extern "C" int igx_groupby_set_mode(igx_table *t, uint32_t mode) {
@@ -1059,6 +1071,7 @@ static int fin_apply(igx_table *t) {
     const uint32_t spilled = reinterpret_cast<const uint32_t *>(h)[1];   // a region overflowed
     t->claims_last = h[4];
     t->gen_keys = h[5];
+    for (int x = 0; x < 4; ++x) t->log_last[x] = h[LOG_STAT_WORD + x];
     if (h[4] == ng || h[5] == ~0ull) t->seed_left = 0;   // a generation started or ended: fresh seeds
     const auto &f = t->fin_snap;   // the interval this read-back belongs to
     if (spilled && f.region) t->region_off = DIRECT_RUN + 1;
@@ -1172,6 +1185,15 @@ extern "C" int igx_groupby_info(igx_table *t, igx_groupby_info_t *out) {
     out->claims = t->claims_last;
     out->gen_keys = t->gen_keys;
     out->persist = t->persist ? 1u : 0u;
+    return IGX_OK;
+}
+
+extern "C" int igx_groupby_log_stats(igx_table *t, igx_groupby_log_stats_t *out) {
+    if (!t || !out) return IGX_EINVAL;
+    out->logged = t->log_last[0];
+    out->fallback_value = t->log_last[1];
+    out->fallback_log_full = t->log_last[2];
+    out->fallback_bucket_full = t->log_last[3];
     return IGX_OK;
 }
 

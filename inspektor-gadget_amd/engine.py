@@ -260,6 +260,14 @@ class Table:
         self.ctx.check(self.ctx.L.igx_groupby_info(self.h, C.byref(v)))
         return {f: getattr(v, f) for f, _ in GroupbyInfo._fields_ if f != "pad"}
 
+    def log_stats(self):
+        """igx_groupby_log_stats: the update log's counters of the last collected finalize's
+        interval (logged records and the three fallback counts), as a dict."""
+        from ._abi import GroupbyLogStats
+        v = GroupbyLogStats()
+        self.ctx.check(self.ctx.L.igx_groupby_log_stats(self.h, C.byref(v)))
+        return {f: getattr(v, f) for f, _ in GroupbyLogStats._fields_}
+
     def rowplan(self):
         """igx_groupby_rowplan: the row plan the last cached update ran (0 general, 1 top tcp,
         2 top file)."""
