@@ -49,6 +49,48 @@ int igx_scratch(igx_ctx *ctx, size_t bytes, void **out) {
     return IGX_OK;
 }
 
+int igx_side(igx_ctx *ctx, size_t bytes, void **out) {
+    if (bytes > ctx->side_bytes) {
+        IGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const size_t want = igx_align(std::max(bytes, ctx->side_bytes * 3 / 2), 1 << 20);
+        (void)igx_side_drop(ctx, 0);
+        if (hipMalloc(&ctx->side, want) != hipSuccess) {
+            ctx->side = nullptr;
+            (void)hipGetLastError();
+            return igx_fail(ctx, IGX_ENOMEM, "side arena: cannot allocate %zu bytes", want);
+        }
+        ctx->side_bytes = want;
+    }
+    *out = ctx->side;
+    return IGX_OK;
+}
+
+int igx_side_drop(igx_ctx *ctx, int rc) {
+    if (ctx->side) (void)hipFree(ctx->side);
+    ctx->side = nullptr;
+    ctx->side_bytes = 0;
+    return rc;
+}
+
+int igx_check_rows(igx_ctx *ctx, const char *who, uint64_t a, uint64_t b) {
+    constexpr uint64_t lim = 0xFFFFFFFEull;   // row ids are u32, 0xFFFFFFFF is IGX_NO_COL, and some are held plus one
+    if (a > lim || b > lim || a + b > lim) return igx_fail(ctx, IGX_EINVAL, "%s: more than 2^32 - 2 rows", who);
+    return IGX_OK;
+}
+
+int igx_join_begin(igx_ctx *ctx, const char *who, uint64_t nrows, uint64_t *d_nemit, uint64_t *d_npend) {
+    const int rc = igx_check_rows(ctx, who, nrows);
+    if (rc) return rc;
+    if (!d_nemit || !d_npend) return igx_fail(ctx, IGX_EINVAL, "%s: null count", who);
+    if (((uintptr_t)d_nemit | (uintptr_t)d_npend) & 7)
+        return igx_fail(ctx, IGX_EINVAL, "%s: counts not 8-byte aligned", who);
+    if (nrows == 0) {
+        IGX_HIP(ctx, hipMemsetAsync(d_nemit, 0, 8, ctx->stream));
+        IGX_HIP(ctx, hipMemsetAsync(d_npend, 0, 8, ctx->stream));
+    }
+    return IGX_OK;
+}
+
 int igx_pinned(igx_ctx *ctx, size_t bytes, void **out) {
     if (bytes > ctx->pinned_bytes) {
         IGX_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -53,8 +53,11 @@ int igx_fail(igx_ctx *ctx, int code, const char *fmt, ...);
 // carved by the caller).  May synchronise the stream when it has to grow.
 int igx_scratch(igx_ctx *ctx, size_t bytes, void **out);
 int igx_pinned(igx_ctx *ctx, size_t bytes, void **out);
-// the side arena (k_traceloop.hip); may synchronise the stream when it has to grow
+// the side arena: what has to outlive a sort, which owns the scratch arena while it runs; may
+// synchronise the stream when it has to grow
 int igx_side(igx_ctx *ctx, size_t bytes, void **out);
+// frees it and returns rc: nothing of a failed call stays allocated
+int igx_side_drop(igx_ctx *ctx, int rc);
 
 static inline size_t igx_align(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -147,20 +150,64 @@ int launch_sort_perm(igx_ctx *ctx, const SortPlanKey *keys, uint32_t nkeys, uint
                      uint32_t pos_stride = 8, const GoSortKey *gokeys = nullptr, uint32_t ngokeys = 0,
                      const uint64_t *d_nrows = nullptr, TopkHint *hint = nullptr);
 
-// k_lwjoin.hip's pipeline in two halves, for the joins composed of it (k_chainjoin.hip).  A row's
-// flag byte after lw_join_mark: LW_F_TAKE (an emitting TAKE_A), LW_F_LIVE (still in a register), 0.
-constexpr uint8_t LW_F_TAKE = 1, LW_F_LIVE = 2;
-struct LwWork {
-    uint8_t *flags;      // nrows bytes, scratch arena
-    uint2 *t_pair;       // per emitting TAKE_A row: (A row, B row or IGX_NO_COL)
-    uint32_t *perm;
-    uint32_t *cnt_t, *cnt_p;
-    uint64_t *off_t, *off_p;
+// a u64 column as the sort's key
+static inline SortPlanKey sort_key_u64(const uint64_t *col) {
+    SortPlanKey k{};
+    k.ptr = reinterpret_cast<const uint8_t *>(col);
+    k.width = 8;
+    k.kind = IGX_KIND_UINT;
+    k.words = 2;
+    k.stride = 8;
+    return k;
+}
+
+// Hands out an arena's pieces in order, each rounded up to 256 bytes.  Over a null base it only
+// adds up `used`: the same calls size the arena first and carve it afterwards.
+struct IgxCarve {
+    char *base;
+    size_t used = 0;
+    template <class T>
+    T *take(size_t bytes) {
+        T *p = base ? reinterpret_cast<T *>(base + used) : nullptr;
+        used += igx_align(bytes, 256);
+        return p;
+    }
 };
+
+// What the joins' entry points check first; `who` prefixes the messages.
+// a, b and a + b are at most 2^32 - 2 rows
+int igx_check_rows(igx_ctx *ctx, const char *who, uint64_t a, uint64_t b = 0);
+// that for nrows, then the two device counts: non-null, 8-byte aligned, and zeroed if nrows == 0
+// (the caller returns on a non-zero code or on nrows == 0)
+int igx_join_begin(igx_ctx *ctx, const char *who, uint64_t nrows, uint64_t *d_nemit, uint64_t *d_npend);
+
+// The pipeline of the sorted-run joins by key in two halves (k_join.hip).  A row's flag byte after
+// join_mark: JOIN_F_EMIT (it emits, with its pair), JOIN_F_LIVE (its run still holds it), 0.
+constexpr uint8_t JOIN_F_EMIT = 1, JOIN_F_LIVE = 2;
+struct JoinWork {        // all of it in the scratch arena
+    uint8_t *code;       // one byte per sorted position, whole tiles of 2048
+    uint8_t *flags;      // nrows bytes
+    uint2 *pair;         // per emitting row: (A row, B row or IGX_NO_COL)
+    void *sums, *carry;  // one summary per tile each
+    uint32_t *cnt_e, *cnt_p;
+    uint64_t *off_e, *off_p;
+};
+// a join's code / summary / carry / apply launches over the rows in perm's order
+typedef void (*JoinPasses)(hipStream_t st, const uint64_t *key, const uint8_t *kind, const uint8_t *valid,
+                           const uint32_t *perm, uint64_t nrows, const JoinWork &w);
+// perm (nrows entries) receives the order; only join_mark's own launches read it
+int join_mark(igx_ctx *ctx, size_t sum_bytes, JoinPasses passes, const uint64_t *key, const uint8_t *kind,
+              const uint8_t *valid, uint64_t nrows, uint32_t *perm, JoinWork *w);
+// The flagged rows in stream order; b_row (and delta) may be where perm was.  With delta,
+// delta[o] = ts[emitting row] - ts[its A row].
+int join_emit(igx_ctx *ctx, const JoinWork *w, uint64_t nrows, uint32_t *emit_row, uint32_t *a_row, uint32_t *b_row,
+              uint64_t *d_nemit, uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend,
+              const uint64_t *ts = nullptr, uint64_t *delta = nullptr);
+// the last-writer join's first half (k_lwjoin.hip), for the joins composed of it (k_chainjoin.hip);
+// its flags: LW_F_TAKE (an emitting TAKE_A), LW_F_LIVE (still in a register)
+constexpr uint8_t LW_F_TAKE = JOIN_F_EMIT, LW_F_LIVE = JOIN_F_LIVE;
 int lw_join_mark(igx_ctx *ctx, const uint64_t *key, const uint8_t *kind, const uint8_t *valid, uint64_t nrows,
-                 uint32_t *perm, LwWork *w);
-int lw_join_emit(igx_ctx *ctx, const LwWork *w, uint64_t nrows, uint32_t *take_row, uint32_t *a_row,
-                 uint32_t *b_row, uint64_t *d_ntake, uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend);
+                 uint32_t *perm, JoinWork *w);
 
 // data (device, n rows in the pre-sort order) sorted in place by Go 1.19 SliceStable, pass by pass
 int launch_go_stable(igx_ctx *ctx, const GoSortKey *keys, uint32_t nkeys, uint64_t nrows, const uint8_t *valid,

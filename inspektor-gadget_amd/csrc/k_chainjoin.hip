@@ -13,7 +13,7 @@
 //   stage 2  on key2.  A DROP is a TAKE_A whose emission nobody wants: the register is empty
 //            afterwards either way, which is all a delete has to do.
 //   merge    (k_cj_merge) in place on stage 2's flags: an emitting DROP loses its flag, a pending
-//            ENTER gets the live flag, and the compaction of k_lwjoin.hip (lw_join_emit) writes
+//            ENTER gets the live flag, and the joins' compaction (join_emit, k_join.hip) writes
 //            emissions and both maps' pending rows out in stream order.
 //
 // The kind column and the order live in the side arena (a sort owns the scratch arena while it
@@ -69,14 +69,6 @@ __global__ __launch_bounds__(TB) void k_cj_merge(const uint8_t *__restrict__ kin
     flags2[i] = o;
 }
 
-// nothing of a failed call stays allocated
-int cj_drop_side(igx_ctx *ctx, int rc) {
-    if (ctx->side) (void)hipFree(ctx->side);
-    ctx->side = nullptr;
-    ctx->side_bytes = 0;
-    return rc;
-}
-
 }  // namespace
 
 extern "C" int igx_chain_join_tile(void) { return igx_lw_join_tile(); }
@@ -85,15 +77,8 @@ extern "C" int igx_chain_join(igx_ctx *ctx, const uint64_t *key1, const uint64_t
                               const uint8_t *valid, uint64_t nrows, uint32_t *take_row, uint32_t *pass_row,
                               uint64_t *d_ntake, uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend) {
     if (!ctx) return IGX_EINVAL;
-    if (nrows > 0xFFFFFFFEull) return igx_fail(ctx, IGX_EINVAL, "chain_join: more than 2^32 - 2 rows");
-    if (!d_ntake || !d_npend) return igx_fail(ctx, IGX_EINVAL, "chain_join: null count");
-    if (((uintptr_t)d_ntake | (uintptr_t)d_npend) & 7)
-        return igx_fail(ctx, IGX_EINVAL, "chain_join: counts not 8-byte aligned");
-    if (nrows == 0) {
-        IGX_HIP(ctx, hipMemsetAsync(d_ntake, 0, 8, ctx->stream));
-        IGX_HIP(ctx, hipMemsetAsync(d_npend, 0, 8, ctx->stream));
-        return IGX_OK;
-    }
+    int rc = igx_join_begin(ctx, "chain_join", nrows, d_ntake, d_npend);
+    if (rc || nrows == 0) return rc;
     if (!key1 || !key2 || !kind || !take_row || !pass_row || (pend_cap && !pend_row))
         return igx_fail(ctx, IGX_EINVAL, "chain_join: null argument");
     if (((uintptr_t)key1 | (uintptr_t)key2) & 7)
@@ -103,20 +88,20 @@ extern "C" int igx_chain_join(igx_ctx *ctx, const uint64_t *key1, const uint64_t
 
     const size_t kind_b = igx_align(nrows, 256);
     void *sd;
-    int rc = igx_side(ctx, kind_b + igx_align(nrows * 4, 256), &sd);
+    rc = igx_side(ctx, kind_b + igx_align(nrows * 4, 256), &sd);
     if (rc) return rc;
     uint8_t *k12 = reinterpret_cast<uint8_t *>(sd);
     // the order of each stage, and where the compaction puts the B rows nobody reads
     uint32_t *perm = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(sd) + kind_b);
     const dim3 grid((unsigned)((nrows + TB - 1) / TB));
 
-    LwWork w;
+    JoinWork w;
     hipLaunchKernelGGL(k_cj_stage1, grid, dim3(TB), 0, ctx->stream, kind, valid, nrows, k12);
     rc = lw_join_mark(ctx, key1, k12, nullptr, nrows, perm, &w);
-    if (rc) return cj_drop_side(ctx, rc);
+    if (rc) return igx_side_drop(ctx, rc);
     hipLaunchKernelGGL(k_cj_handover, grid, dim3(TB), 0, ctx->stream, kind, valid, w.flags, nrows, k12);
     rc = lw_join_mark(ctx, key2, k12, nullptr, nrows, perm, &w);
-    if (rc) return cj_drop_side(ctx, rc);
+    if (rc) return igx_side_drop(ctx, rc);
     hipLaunchKernelGGL(k_cj_merge, grid, dim3(TB), 0, ctx->stream, kind, k12, nrows, w.flags);
-    return lw_join_emit(ctx, &w, nrows, take_row, pass_row, perm, d_ntake, pend_row, pend_cap, d_npend);
+    return join_emit(ctx, &w, nrows, take_row, pass_row, perm, d_ntake, pend_row, pend_cap, d_npend);
 }

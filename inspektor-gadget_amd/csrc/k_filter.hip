@@ -13,7 +13,7 @@
 // Algorithmic bytes per row = sum of predicate column widths + 4 per survivor.
 #include <cstdlib>
 
-#include "k_common.h"
+#include "k_scan.h"
 
 namespace {
 
@@ -128,25 +128,8 @@ __global__ __launch_bounds__(TB) void k_filter_mark_int(DevPreds dp, const uint8
 __global__ __launch_bounds__(1024) void k_scan_counts(const uint32_t *__restrict__ cnt, uint64_t m,
                                                       uint64_t *__restrict__ off,
                                                       uint64_t *__restrict__ total) {
-    __shared__ uint64_t part[1024];
-    const uint64_t per = (m + 1023) / 1024;
-    const uint64_t b = threadIdx.x * per, e = min(m, b + per);
-    uint64_t s = 0;
-    for (uint64_t i = b; i < e; ++i) s += cnt[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        uint64_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint64_t run = threadIdx.x ? part[threadIdx.x - 1] : 0;
-    for (uint64_t i = b; i < e; ++i) {
-        off[i] = run;
-        run += cnt[i];
-    }
-    if (threadIdx.x == 1023) *total = part[1023];
+    const uint64_t sum = scan_counts(cnt, m, off);
+    if (threadIdx.x == 1023) *total = sum;
 }
 
 __global__ __launch_bounds__(TB) void k_filter_compact(const uint64_t *__restrict__ mask,

@@ -16,13 +16,13 @@
 //   apply    per tile, from its carry: every TAKE_A's outcome (its A and B rows, one 8-byte
 //            store at the take row) and, at the last row of each run, the rows the registers
 //            hold; one flag byte per row
-//   count / scan / compact   the flagged rows written out in stream order
+//   count / scan / compact   the flagged rows written out in stream order (k_join.hip)
 //
 // Every launch is a plain grid; no workgroup waits on another.  Algorithmic bytes per row:
 // DESIGN.md §4.  The pipeline is callable in two halves (igx_internal.h: lw_join_mark through
-// apply, lw_join_emit from count on) for the joins composed of it (k_chainjoin.hip); igx_lw_join
+// apply, join_emit from count on) for the joins composed of it (k_chainjoin.hip); igx_lw_join
 // is the two back to back.
-#include "k_common.h"
+#include "k_scan.h"
 #include "k_lwjoin.h"
 
 static_assert(IGX_LW_SET_A == LW_SET_A && IGX_LW_SET_B == LW_SET_B && IGX_LW_CLEAR_B == LW_CLEAR_B &&
@@ -31,12 +31,7 @@ static_assert(IGX_LW_SET_A == LW_SET_A && IGX_LW_SET_B == LW_SET_B && IGX_LW_CLE
 
 namespace {
 
-constexpr int TB = 256;
-constexpr int RPT = 8;                // consecutive positions per thread
-constexpr int LW_TILE = TB * RPT;     // 2048 positions per scan tile
-constexpr int CRPT = 4;
-constexpr int CTILE = TB * CRPT;      // 1024 rows per compaction tile
-constexpr int CGROUPS = CTILE / 64;   // wave-row groups per compaction tile
+constexpr int TB = SCAN_TB, RPT = SCAN_RPT, LW_TILE = SCAN_TILE;
 constexpr uint8_t F_TAKE = LW_F_TAKE, F_LIVE = LW_F_LIVE;
 
 __device__ __forceinline__ LwSum lw_shfl_up(const LwSum &v, int o) {
@@ -47,6 +42,13 @@ __device__ __forceinline__ LwSum lw_shfl_up(const LwSum &v, int o) {
     r.pad = 0;
     return r;
 }
+
+struct LwOp {
+    using T = LwSum;
+    static __device__ __forceinline__ T identity() { return T{}; }
+    static __device__ __forceinline__ T combine(const T &x, const T &y) { return lw_combine(x, y); }
+    static __device__ __forceinline__ T shfl_up(const T &v, int o) { return lw_shfl_up(v, o); }
+};
 
 __global__ __launch_bounds__(TB) void k_lw_code(const uint64_t *__restrict__ key, const uint8_t *__restrict__ kind,
                                                 const uint8_t *__restrict__ valid,
@@ -75,30 +77,6 @@ __device__ __forceinline__ LwSum lw_thread_sum(const uint8_t *__restrict__ code,
     return acc;
 }
 
-// Exclusive scan of the threads' summaries over the workgroup; *total is the tile's summary
-// (valid in every thread).
-__device__ __forceinline__ LwSum lw_block_scan(const LwSum &mine, LwSum *wsum, LwSum *total) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    LwSum inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const LwSum lo = lw_shfl_up(inc, o);
-        if (lane >= (uint32_t)o) inc = lw_combine(lo, inc);
-    }
-    if (lane == 63) wsum[wave] = inc;
-    LwSum exc = lw_shfl_up(inc, 1);
-    if (lane == 0) exc = LwSum{};
-    __syncthreads();
-    LwSum pre{}, tot{};
-#pragma unroll
-    for (int w = 0; w < TB / 64; ++w) {
-        if ((uint32_t)w == wave) pre = tot;
-        tot = lw_combine(tot, wsum[w]);
-    }
-    *total = tot;
-    return lw_combine(pre, exc);
-}
-
 __global__ __launch_bounds__(TB) void k_lw_summary(const uint8_t *__restrict__ code, uint64_t n,
                                                    LwSum *__restrict__ sums) {
     __shared__ LwSum wsum[TB / 64];
@@ -106,32 +84,14 @@ __global__ __launch_bounds__(TB) void k_lw_summary(const uint8_t *__restrict__ c
     const uint64_t p0 = (uint64_t)blockIdx.x * LW_TILE + (uint64_t)threadIdx.x * RPT;
     const LwSum mine = lw_thread_sum(code, p0, n, c);
     LwSum total;
-    (void)lw_block_scan(mine, wsum, &total);
+    (void)block_scan<LwOp>(mine, wsum, &total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 // carry[t] = the summary of tiles [0, t); one workgroup of 1024
 __global__ __launch_bounds__(1024) void k_lw_carry(const LwSum *__restrict__ sums, uint64_t m,
                                                    LwSum *__restrict__ carry) {
-    __shared__ LwSum part[1024];
-    const uint64_t per = (m + 1023) / 1024;
-    const uint64_t b = min(m, (uint64_t)threadIdx.x * per), e = min(m, b + per);
-    LwSum s{};
-    for (uint64_t i = b; i < e; ++i) s = lw_combine(s, sums[i]);
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        LwSum lo{};
-        if (threadIdx.x >= (unsigned)d) lo = part[threadIdx.x - d];
-        __syncthreads();
-        if (threadIdx.x >= (unsigned)d) part[threadIdx.x] = lw_combine(lo, part[threadIdx.x]);
-        __syncthreads();
-    }
-    LwSum run = threadIdx.x ? part[threadIdx.x - 1] : LwSum{};
-    for (uint64_t i = b; i < e; ++i) {
-        carry[i] = run;
-        run = lw_combine(run, sums[i]);
-    }
+    tile_carry<LwOp, 1024>(sums, m, carry);
 }
 
 __global__ __launch_bounds__(TB) void k_lw_apply(const uint8_t *__restrict__ code,
@@ -143,7 +103,7 @@ __global__ __launch_bounds__(TB) void k_lw_apply(const uint8_t *__restrict__ cod
     const uint64_t p0 = (uint64_t)blockIdx.x * LW_TILE + (uint64_t)threadIdx.x * RPT;
     const LwSum mine = lw_thread_sum(code, p0, n, c);
     LwSum total;
-    const LwSum exc = lw_block_scan(mine, wsum, &total);
+    const LwSum exc = block_scan<LwOp>(mine, wsum, &total);
     if (p0 >= n) return;
     LwSum st = lw_combine(carry[blockIdx.x], exc);
     // the code after this thread's last one says whether that one ends its run
@@ -168,106 +128,16 @@ __global__ __launch_bounds__(TB) void k_lw_apply(const uint8_t *__restrict__ cod
     }
 }
 
-// ---- the flagged rows in stream order ---------------------------------------------------------
-__global__ __launch_bounds__(TB) void k_lw_count(const uint8_t *__restrict__ flags, uint64_t n,
-                                                 uint32_t *__restrict__ cnt_t, uint32_t *__restrict__ cnt_p) {
-    __shared__ uint32_t wt[TB / 64], wp[TB / 64];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint32_t t = 0, p = 0;
-#pragma unroll
-    for (int j = 0; j < CRPT; ++j) {
-        const uint64_t row = (uint64_t)blockIdx.x * CTILE + (uint64_t)j * TB + threadIdx.x;
-        const uint32_t f = row < n ? flags[row] : 0u;
-        t += __popcll(__ballot(f == F_TAKE));
-        p += __popcll(__ballot(f == F_LIVE));
-    }
-    if (lane == 0) {
-        wt[wave] = t;
-        wp[wave] = p;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t st = 0, sp = 0;
-        for (int w = 0; w < TB / 64; ++w) {
-            st += wt[w];
-            sp += wp[w];
-        }
-        cnt_t[blockIdx.x] = st;
-        cnt_p[blockIdx.x] = sp;
-    }
-}
-
-// exclusive scan of cnt[0..m) -> off[0..m), total -> *total; block 0 the TAKE counts, block 1
-// the live counts (each one workgroup of 1024 on its own array)
-__global__ __launch_bounds__(1024) void k_lw_scan(const uint32_t *__restrict__ cnt_t,
-                                                  const uint32_t *__restrict__ cnt_p, uint64_t m,
-                                                  uint64_t *__restrict__ off_t, uint64_t *__restrict__ off_p,
-                                                  uint64_t *__restrict__ tot_t, uint64_t *__restrict__ tot_p) {
-    __shared__ uint64_t part[1024];
-    const uint32_t *cnt = blockIdx.x ? cnt_p : cnt_t;
-    uint64_t *off = blockIdx.x ? off_p : off_t;
-    const uint64_t per = (m + 1023) / 1024;
-    const uint64_t b = min(m, (uint64_t)threadIdx.x * per), e = min(m, b + per);
-    uint64_t s = 0;
-    for (uint64_t i = b; i < e; ++i) s += cnt[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const uint64_t v = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint64_t run = threadIdx.x ? part[threadIdx.x - 1] : 0;
-    for (uint64_t i = b; i < e; ++i) {
-        off[i] = run;
-        run += cnt[i];
-    }
-    if (threadIdx.x == 1023) *(blockIdx.x ? tot_p : tot_t) = part[1023];
-}
-
-__global__ __launch_bounds__(TB) void k_lw_compact(const uint8_t *__restrict__ flags, uint64_t n,
-                                                   const uint64_t *__restrict__ off_t,
-                                                   const uint64_t *__restrict__ off_p,
-                                                   const uint2 *__restrict__ t_pair, uint32_t *__restrict__ take_row,
-                                                   uint32_t *__restrict__ a_row, uint32_t *__restrict__ b_row,
-                                                   uint32_t *__restrict__ pend_row, uint64_t pend_cap) {
-    __shared__ uint32_t gt[CGROUPS], gp[CGROUPS];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint32_t f[CRPT];
-    uint64_t bt[CRPT], bp[CRPT];
-#pragma unroll
-    for (int j = 0; j < CRPT; ++j) {
-        const uint64_t row = (uint64_t)blockIdx.x * CTILE + (uint64_t)j * TB + threadIdx.x;
-        f[j] = row < n ? flags[row] : 0u;
-        bt[j] = __ballot(f[j] == F_TAKE);
-        bp[j] = __ballot(f[j] == F_LIVE);
-        if (lane == 0) {   // group j * 4 + wave holds rows [64 * group, 64 * group + 64) of the tile
-            gt[j * (TB / 64) + wave] = __popcll(bt[j]);
-            gp[j * (TB / 64) + wave] = __popcll(bp[j]);
-        }
-    }
-    __syncthreads();
-    const uint64_t base_t = off_t[blockIdx.x], base_p = off_p[blockIdx.x];
-#pragma unroll
-    for (int j = 0; j < CRPT; ++j) {
-        if (f[j] == 0) continue;
-        const uint32_t g = j * (TB / 64) + wave;
-        const uint32_t row = (uint32_t)((uint64_t)blockIdx.x * CTILE + (uint64_t)j * TB + threadIdx.x);
-        uint32_t pre = 0;
-        if (f[j] == F_TAKE) {
-            for (uint32_t w = 0; w < g; ++w) pre += gt[w];
-            const uint64_t o = base_t + pre + __popcll(bt[j] & lanemask_lt());
-            const uint2 pr = t_pair[row];
-            take_row[o] = row;
-            a_row[o] = pr.x;
-            b_row[o] = pr.y;
-        } else {
-            for (uint32_t w = 0; w < g; ++w) pre += gp[w];
-            const uint64_t o = base_p + pre + __popcll(bp[j] & lanemask_lt());
-            if (o < pend_cap) pend_row[o] = row;
-        }
-    }
+// the four passes of join_mark
+void lw_passes(hipStream_t st, const uint64_t *key, const uint8_t *kind, const uint8_t *valid, const uint32_t *perm,
+               uint64_t nrows, const JoinWork &w) {
+    const dim3 tiles((unsigned)((nrows + LW_TILE - 1) / LW_TILE));
+    LwSum *sums = static_cast<LwSum *>(w.sums), *carry = static_cast<LwSum *>(w.carry);
+    hipLaunchKernelGGL(k_lw_code, dim3((unsigned)((nrows + TB - 1) / TB)), dim3(TB), 0, st, key, kind, valid, perm,
+                       nrows, w.code);
+    hipLaunchKernelGGL(k_lw_summary, tiles, dim3(TB), 0, st, w.code, nrows, sums);
+    hipLaunchKernelGGL(k_lw_carry, dim3(1), dim3(1024), 0, st, sums, (uint64_t)tiles.x, carry);
+    hipLaunchKernelGGL(k_lw_apply, tiles, dim3(TB), 0, st, w.code, perm, nrows, carry, w.flags, w.pair);
 }
 
 }  // namespace
@@ -275,81 +145,18 @@ __global__ __launch_bounds__(TB) void k_lw_compact(const uint8_t *__restrict__ f
 extern "C" int igx_lw_join_tile(void) { return LW_TILE; }
 
 // The pipeline through the apply pass: w->flags[r] says what row r ended as (LW_F_TAKE: an emitting
-// TAKE_A, with its A and B rows in w->t_pair[r]; LW_F_LIVE: still held in a register), all of it in
-// the scratch arena.  perm (nrows entries) holds the order and must outlive lw_join_emit.
+// TAKE_A, with its A and B rows in w->pair[r]; LW_F_LIVE: still held in a register).
 int lw_join_mark(igx_ctx *ctx, const uint64_t *key, const uint8_t *kind, const uint8_t *valid, uint64_t nrows,
-                 uint32_t *perm, LwWork *w) {
-    const uint64_t ntiles = (nrows + LW_TILE - 1) / LW_TILE, ctiles = (nrows + CTILE - 1) / CTILE;
-    const size_t code_b = igx_align(ntiles * LW_TILE, 256), flag_b = igx_align(nrows, 256);
-    const size_t pair_b = igx_align(nrows * 8, 256), sum_b = igx_align(ntiles * sizeof(LwSum), 256);
-    const size_t cnt_b = igx_align(ctiles * 4, 256), off_b = igx_align(ctiles * 8, 256);
-    const size_t need = code_b + flag_b + pair_b + 2 * sum_b + 2 * cnt_b + 2 * off_b;
-    void *s;
-    // ask before the sort, so that an arena that has to grow does it before the order exists
-    int rc = igx_scratch(ctx, need, &s);
-    if (rc) return rc;
-    SortPlanKey sk{};
-    sk.ptr = reinterpret_cast<const uint8_t *>(key);
-    sk.width = 8;
-    sk.kind = IGX_KIND_UINT;
-    sk.words = 2;
-    sk.stride = 8;
-    rc = launch_sort_perm(ctx, &sk, 1, nrows, nullptr, false, nullptr, perm, 0, nullptr);
-    if (rc) return rc;
-    rc = igx_scratch(ctx, need, &s);
-    if (rc) return rc;
-    char *c = reinterpret_cast<char *>(s);
-    uint8_t *code = reinterpret_cast<uint8_t *>(c);
-    uint8_t *flags = reinterpret_cast<uint8_t *>(c + code_b);
-    uint2 *t_pair = reinterpret_cast<uint2 *>(c + code_b + flag_b);
-    LwSum *sums = reinterpret_cast<LwSum *>(c + code_b + flag_b + pair_b);
-    LwSum *carry = reinterpret_cast<LwSum *>(c + code_b + flag_b + pair_b + sum_b);
-    char *q = c + code_b + flag_b + pair_b + 2 * sum_b;
-    w->flags = flags;
-    w->t_pair = t_pair;
-    w->perm = perm;
-    w->cnt_t = reinterpret_cast<uint32_t *>(q);
-    w->cnt_p = reinterpret_cast<uint32_t *>(q + cnt_b);
-    w->off_t = reinterpret_cast<uint64_t *>(q + 2 * cnt_b);
-    w->off_p = reinterpret_cast<uint64_t *>(q + 2 * cnt_b + off_b);
-
-    IGX_HIP(ctx, hipMemsetAsync(flags, 0, flag_b, ctx->stream));
-    hipLaunchKernelGGL(k_lw_code, dim3((unsigned)((nrows + TB - 1) / TB)), dim3(TB), 0, ctx->stream, key, kind, valid,
-                       perm, nrows, code);
-    hipLaunchKernelGGL(k_lw_summary, dim3((unsigned)ntiles), dim3(TB), 0, ctx->stream, code, nrows, sums);
-    hipLaunchKernelGGL(k_lw_carry, dim3(1), dim3(1024), 0, ctx->stream, sums, ntiles, carry);
-    hipLaunchKernelGGL(k_lw_apply, dim3((unsigned)ntiles), dim3(TB), 0, ctx->stream, code, perm, nrows, carry, flags,
-                       t_pair);
-    return IGX_OK;
-}
-
-// The flagged rows of w written out in stream order; b_row may be the perm that lw_join_mark used.
-int lw_join_emit(igx_ctx *ctx, const LwWork *w, uint64_t nrows, uint32_t *take_row, uint32_t *a_row,
-                 uint32_t *b_row, uint64_t *d_ntake, uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend) {
-    const uint64_t ctiles = (nrows + CTILE - 1) / CTILE;
-    hipLaunchKernelGGL(k_lw_count, dim3((unsigned)ctiles), dim3(TB), 0, ctx->stream, w->flags, nrows, w->cnt_t,
-                       w->cnt_p);
-    hipLaunchKernelGGL(k_lw_scan, dim3(2), dim3(1024), 0, ctx->stream, w->cnt_t, w->cnt_p, ctiles, w->off_t, w->off_p,
-                       d_ntake, d_npend);
-    hipLaunchKernelGGL(k_lw_compact, dim3((unsigned)ctiles), dim3(TB), 0, ctx->stream, w->flags, nrows, w->off_t,
-                       w->off_p, w->t_pair, take_row, a_row, b_row, pend_row, pend_cap);
-    IGX_HIP(ctx, hipGetLastError());
-    return IGX_OK;
+                 uint32_t *perm, JoinWork *w) {
+    return join_mark(ctx, sizeof(LwSum), lw_passes, key, kind, valid, nrows, perm, w);
 }
 
 extern "C" int igx_lw_join(igx_ctx *ctx, const uint64_t *key, const uint8_t *kind, const uint8_t *valid,
                            uint64_t nrows, uint32_t *take_row, uint32_t *a_row, uint32_t *b_row, uint64_t *d_ntake,
                            uint32_t *pend_row, uint64_t pend_cap, uint64_t *d_npend) {
     if (!ctx) return IGX_EINVAL;
-    if (nrows > 0xFFFFFFFEull) return igx_fail(ctx, IGX_EINVAL, "lw_join: more than 2^32 - 2 rows");
-    if (!d_ntake || !d_npend) return igx_fail(ctx, IGX_EINVAL, "lw_join: null count");
-    if (((uintptr_t)d_ntake | (uintptr_t)d_npend) & 7)
-        return igx_fail(ctx, IGX_EINVAL, "lw_join: counts not 8-byte aligned");
-    if (nrows == 0) {
-        IGX_HIP(ctx, hipMemsetAsync(d_ntake, 0, 8, ctx->stream));
-        IGX_HIP(ctx, hipMemsetAsync(d_npend, 0, 8, ctx->stream));
-        return IGX_OK;
-    }
+    int rc = igx_join_begin(ctx, "lw_join", nrows, d_ntake, d_npend);
+    if (rc || nrows == 0) return rc;
     if (!key || !kind || !take_row || !a_row || !b_row || (pend_cap && !pend_row))
         return igx_fail(ctx, IGX_EINVAL, "lw_join: null argument");
     if ((uintptr_t)key & 7) return igx_fail(ctx, IGX_EINVAL, "lw_join: key must be 8-byte aligned");
@@ -358,8 +165,8 @@ extern "C" int igx_lw_join(igx_ctx *ctx, const uint64_t *key, const uint8_t *kin
     // The order lives in b_row (read by the code and apply passes, written by the compaction,
     // which no longer needs it) while the scratch arena, which the sort uses too, is handed from
     // the sort to the passes.
-    LwWork w;
-    const int rc = lw_join_mark(ctx, key, kind, valid, nrows, b_row, &w);
+    JoinWork w;
+    rc = lw_join_mark(ctx, key, kind, valid, nrows, b_row, &w);
     if (rc) return rc;
-    return lw_join_emit(ctx, &w, nrows, take_row, a_row, b_row, d_ntake, pend_row, pend_cap, d_npend);
+    return join_emit(ctx, &w, nrows, take_row, a_row, b_row, d_ntake, pend_row, pend_cap, d_npend);
 }

@@ -26,7 +26,7 @@
 // lane waits for another's store; every probe loop ends after S slots.
 #include <algorithm>
 
-#include "k_common.h"
+#include "k_scan.h"
 #include "k_stack.h"
 
 struct igx_intern {
@@ -171,26 +171,9 @@ __global__ __launch_bounds__(TB) void k_st_flag(const uint32_t *__restrict__ out
 // exclusive scan of cnt[0..m) -> off[0..m) (one workgroup of 1024), then the add's bookkeeping
 __global__ __launch_bounds__(1024) void k_st_scan(const uint32_t *__restrict__ cnt, uint64_t m,
                                                   uint64_t *__restrict__ off, uint64_t *state, uint64_t cap) {
-    __shared__ uint64_t part[1024];
-    const uint64_t per = (m + 1023) / 1024;
-    const uint64_t b = min(m, (uint64_t)threadIdx.x * per), e = min(m, b + per);
-    uint64_t s = 0;
-    for (uint64_t i = b; i < e; ++i) s += cnt[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const uint64_t v = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint64_t run = threadIdx.x ? part[threadIdx.x - 1] : 0;
-    for (uint64_t i = b; i < e; ++i) {
-        off[i] = run;
-        run += cnt[i];
-    }
+    const uint64_t total = scan_counts(cnt, m, off);
     if (threadIdx.x == 1023) {
-        const uint64_t base = state[ST_COUNT], fresh = part[1023];
+        const uint64_t base = state[ST_COUNT], fresh = total;
         const bool over = state[ST_NOSLOT] != 0 || base + fresh > cap;
         state[ST_BASE] = base;
         state[ST_NEW] = fresh;

@@ -21,16 +21,12 @@
 //
 // Every launch is a plain grid; no workgroup waits on another, and the only atomic is the integer
 // add of the event count.  Algorithmic bytes per row: DESIGN.md §4.
-#include <algorithm>
-
-#include "k_common.h"
+#include "k_scan.h"
 #include "k_traceloop.h"
 
 namespace {
 
-constexpr int TB = 256;
-constexpr int RPT = 8;                // consecutive positions per thread
-constexpr int TL_TILE = TB * RPT;     // 2048 positions per scan tile
+constexpr int TB = SCAN_TB, RPT = SCAN_RPT, TL_TILE = SCAN_TILE;
 constexpr int CARRY_T = 512;
 
 struct TlIn {
@@ -125,28 +121,12 @@ __device__ __forceinline__ TlSum tl_thread_sum(const uint8_t *__restrict__ code,
     return acc;
 }
 
-// Exclusive scan of the threads' summaries over the workgroup; *total is the tile's summary.
-__device__ __forceinline__ TlSum tl_block_scan(const TlSum &mine, TlSum *wsum, TlSum *total) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    TlSum inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const TlSum lo = tl_shfl_up(inc, o);
-        if (lane >= (uint32_t)o) inc = tl_combine(lo, inc);
-    }
-    if (lane == 63) wsum[wave] = inc;
-    TlSum exc = tl_shfl_up(inc, 1);
-    if (lane == 0) exc = tl_identity();
-    __syncthreads();
-    TlSum pre = tl_identity(), tot = tl_identity();
-#pragma unroll
-    for (int w = 0; w < TB / 64; ++w) {
-        if ((uint32_t)w == wave) pre = tot;
-        tot = tl_combine(tot, wsum[w]);
-    }
-    *total = tot;
-    return tl_combine(pre, exc);
-}
+struct TlOp {
+    using T = TlSum;
+    static __device__ __forceinline__ T identity() { return tl_identity(); }
+    static __device__ __forceinline__ T combine(const T &x, const T &y) { return tl_combine(x, y); }
+    static __device__ __forceinline__ T shfl_up(const T &v, int o) { return tl_shfl_up(v, o); }
+};
 
 __global__ __launch_bounds__(TB) void k_tl_summary(const uint8_t *__restrict__ code,
                                                    const uint32_t *__restrict__ perm, uint64_t n,
@@ -156,32 +136,14 @@ __global__ __launch_bounds__(TB) void k_tl_summary(const uint8_t *__restrict__ c
     const uint64_t p0 = (uint64_t)blockIdx.x * TL_TILE + (uint64_t)threadIdx.x * RPT;
     const TlSum mine = tl_thread_sum(code, perm, p0, n, c, row);
     TlSum total;
-    (void)tl_block_scan(mine, wsum, &total);
+    (void)block_scan<TlOp>(mine, wsum, &total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 // carry[t] = the summary of tiles [0, t); one workgroup
 __global__ __launch_bounds__(CARRY_T) void k_tl_carry(const TlSum *__restrict__ sums, uint64_t m,
                                                       TlSum *__restrict__ carry) {
-    __shared__ TlSum part[CARRY_T];
-    const uint64_t per = (m + CARRY_T - 1) / CARRY_T;
-    const uint64_t b = min(m, (uint64_t)threadIdx.x * per), e = min(m, b + per);
-    TlSum s = tl_identity();
-    for (uint64_t i = b; i < e; ++i) s = tl_combine(s, sums[i]);
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = 1; d < CARRY_T; d <<= 1) {
-        TlSum lo = tl_identity();
-        if (threadIdx.x >= (unsigned)d) lo = part[threadIdx.x - d];
-        __syncthreads();
-        if (threadIdx.x >= (unsigned)d) part[threadIdx.x] = tl_combine(lo, part[threadIdx.x]);
-        __syncthreads();
-    }
-    TlSum run = threadIdx.x ? part[threadIdx.x - 1] : tl_identity();
-    for (uint64_t i = b; i < e; ++i) {
-        carry[i] = run;
-        run = tl_combine(run, sums[i]);
-    }
+    tile_carry<TlOp, CARRY_T>(sums, m, carry);
 }
 
 // At the last position of every group: what the group comes to, at its number.
@@ -194,7 +156,7 @@ __global__ __launch_bounds__(TB) void k_tl_groups(const uint8_t *__restrict__ co
     const uint64_t p0 = (uint64_t)blockIdx.x * TL_TILE + (uint64_t)threadIdx.x * RPT;
     const TlSum mine = tl_thread_sum(code, perm, p0, n, c, row);
     TlSum total;
-    const TlSum exc = tl_block_scan(mine, wsum, &total);
+    const TlSum exc = block_scan<TlOp>(mine, wsum, &total);
     if (p0 >= n) return;
     TlSum st = tl_combine(carry[blockIdx.x], exc);
     // the code after this thread's last one says whether that one ends its group
@@ -311,25 +273,6 @@ __global__ __launch_bounds__(TB) void k_tl_emit(uint64_t ns, const uint64_t *__r
 
 }  // namespace
 
-// the side arena: what has to outlive a sort, which owns the scratch arena while it runs
-int igx_side(igx_ctx *ctx, size_t bytes, void **out) {
-    if (bytes > ctx->side_bytes) {
-        IGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const size_t want = igx_align(std::max(bytes, ctx->side_bytes * 3 / 2), 1 << 20);
-        if (ctx->side) (void)hipFree(ctx->side);
-        ctx->side = nullptr;
-        ctx->side_bytes = 0;
-        if (hipMalloc(&ctx->side, want) != hipSuccess) {
-            ctx->side = nullptr;
-            (void)hipGetLastError();
-            return igx_fail(ctx, IGX_ENOMEM, "traceloop: cannot allocate %zu bytes", want);
-        }
-        ctx->side_bytes = want;
-    }
-    *out = ctx->side;
-    return IGX_OK;
-}
-
 extern "C" int igx_traceloop_tile(void) { return TL_TILE; }
 
 extern "C" int igx_traceloop_join(igx_ctx *ctx, const uint64_t *mntns, const uint64_t *mono_ts,
@@ -340,8 +283,8 @@ extern "C" int igx_traceloop_join(igx_ctx *ctx, const uint64_t *mntns, const uin
                                   uint32_t *ev_row, uint32_t *ev_exit, uint8_t *ev_class, uint32_t *ev_cont,
                                   uint64_t *d_nev) {
     if (!ctx) return IGX_EINVAL;
-    if (ns > 0xFFFFFFFEull || nc > 0xFFFFFFFEull || ns + nc > 0xFFFFFFFEull)
-        return igx_fail(ctx, IGX_EINVAL, "traceloop_join: more than 2^32 - 2 rows");
+    int rc = igx_check_rows(ctx, "traceloop_join", ns, nc);
+    if (rc) return rc;
     if (!d_nev) return igx_fail(ctx, IGX_EINVAL, "traceloop_join: null count");
     if ((uintptr_t)d_nev & 7) return igx_fail(ctx, IGX_EINVAL, "traceloop_join: count not 8-byte aligned");
     if (ns && (!mono_ts || !sort_ts || !typ || !id || !pid || !ev_row || !ev_exit || !ev_class || !ev_cont))
@@ -366,19 +309,22 @@ extern "C" int igx_traceloop_join(igx_ctx *ctx, const uint64_t *mntns, const uin
     const size_t byte_b = igx_align(ns, 256), gid_b = igx_align(ns * 4, 256);
     const size_t side_need = 3 * key_b + perm_b + gsum_b + 2 * byte_b + gid_b;
     // scratch arena (the sorts' while they run): code | tile summaries | carries
-    const size_t code_b = igx_align(ntiles * TL_TILE, 256), sum_b = igx_align(ntiles * sizeof(TlSum), 256);
-    const size_t need = code_b + 2 * sum_b;
+    uint8_t *code;
+    TlSum *sums, *carry;
+    const auto carve = [&](void *base) {
+        IgxCarve c{reinterpret_cast<char *>(base)};
+        code = c.take<uint8_t>(ntiles * TL_TILE);
+        sums = c.take<TlSum>(ntiles * sizeof(TlSum));
+        carry = c.take<TlSum>(ntiles * sizeof(TlSum));
+        return c.used;
+    };
+    const size_t need = carve(nullptr);
     void *s, *sd;
-    int rc = igx_side(ctx, side_need, &sd);
+    rc = igx_side(ctx, side_need, &sd);
     if (rc) return rc;
     // ask before the sort, so that an arena that has to grow does it before the order exists
     rc = igx_scratch(ctx, need, &s);
-    if (rc) {   // nothing of this call's stays allocated
-        (void)hipFree(ctx->side);
-        ctx->side = nullptr;
-        ctx->side_bytes = 0;
-        return rc;
-    }
+    if (rc) return igx_side_drop(ctx, rc);
     char *d = reinterpret_cast<char *>(sd);
     uint64_t *k_mn = has_mn ? reinterpret_cast<uint64_t *>(d) : nullptr;
     uint64_t *k_ts = reinterpret_cast<uint64_t *>(d + key_b), *k_sub = reinterpret_cast<uint64_t *>(d + 2 * key_b);
@@ -392,24 +338,13 @@ extern "C" int igx_traceloop_join(igx_ctx *ctx, const uint64_t *mntns, const uin
     TlIn in{mntns, mono_ts, typ, id, pid, valid, ns, c_mntns, c_mono_ts, c_index, c_valid, nc};
     hipLaunchKernelGGL(k_tl_pack, dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, ctx->stream, in, k_mn, k_ts, k_sub);
     IGX_HIP(ctx, hipGetLastError());
-    SortPlanKey key[3] = {};
-    uint32_t nk = 0;
-    const uint64_t *cols[3] = {k_mn, k_ts, k_sub};
-    for (int i = has_mn ? 0 : 1; i < 3; ++i) {
-        key[nk].ptr = reinterpret_cast<const uint8_t *>(cols[i]);
-        key[nk].width = 8;
-        key[nk].kind = IGX_KIND_UINT;
-        key[nk].words = 2;
-        key[nk].stride = 8;
-        ++nk;
-    }
-    rc = launch_sort_perm(ctx, key, nk, n, nullptr, false, nullptr, perm, 0, nullptr);
+    const SortPlanKey key[3] = {sort_key_u64(k_mn), sort_key_u64(k_ts), sort_key_u64(k_sub)};
+    const int k0 = has_mn ? 0 : 1;
+    rc = launch_sort_perm(ctx, key + k0, 3 - k0, n, nullptr, false, nullptr, perm, 0, nullptr);
     if (rc) return rc;
     rc = igx_scratch(ctx, need, &s);
     if (rc) return rc;
-    char *c = reinterpret_cast<char *>(s);
-    uint8_t *code = reinterpret_cast<uint8_t *>(c);
-    TlSum *sums = reinterpret_cast<TlSum *>(c + code_b), *carry = reinterpret_cast<TlSum *>(c + code_b + sum_b);
+    (void)carve(s);
 
     IGX_HIP(ctx, hipMemsetAsync(cls, 0xFF, byte_b, ctx->stream));
     IGX_HIP(ctx, hipMemsetAsync(nf, 1, byte_b, ctx->stream));
@@ -429,11 +364,7 @@ extern "C" int igx_traceloop_join(igx_ctx *ctx, const uint64_t *mntns, const uin
     k2[0].kind = IGX_KIND_UINT;
     k2[0].words = 1;
     k2[0].stride = 1;
-    k2[1].ptr = reinterpret_cast<const uint8_t *>(sort_ts);
-    k2[1].width = 8;
-    k2[1].kind = IGX_KIND_UINT;
-    k2[1].words = 2;
-    k2[1].stride = 8;
+    k2[1] = sort_key_u64(sort_ts);
     rc = launch_sort_perm(ctx, k2, 2, ns, nullptr, false, nullptr, ev_row, 0, nullptr);
     if (rc) return rc;
     hipLaunchKernelGGL(k_tl_emit, dim3((unsigned)((ns + TB - 1) / TB)), dim3(TB), 0, ctx->stream, ns, d_nev, cls, t_gid,

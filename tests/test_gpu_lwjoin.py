@@ -2,7 +2,8 @@
 in tests/lwjoin_ref.py: all three output arrays, both counts and the live rows, bit for bit.
 
 Sizes: the contract's hand cases; 0, 1 and the scan tile - 1 / tile / tile + 1 / 3 tiles + 5 rows
-(the tile comes from the library); one key for 70 000 rows (a run across many tiles and workgroups)
+(the tile comes from the library) and 1024 tiles + 1 row (more tiles than the carry and the count
+scan have threads); one key for 70 000 rows (a run across many tiles and workgroups)
 and 70 000 distinct keys; 200 000 rows over 64 keys that differ in byte 7 only, and in byte 0 only
 (the sort's digit plan at both ends); SET_A-heavy, TAKE-only and T T A T T streams; one key whose B
 has to cross every tile boundary between a SET_A at row 0 and a TAKE_A at the last row; a nil mask;
@@ -54,6 +55,15 @@ def test_tile_edges(igx):
         take, b, live = _check(igx, key, kind)
         # floor: 100 emissions, 50 of them with a B row, and 3 pending rows from one tile on
         assert n < tile - 1 or (len(take) > 100 and int((b != R.NONE).sum()) > 50 and len(live) >= 3)
+
+
+def test_more_tiles_than_scan_threads(igx):
+    """1025 scan tiles and 2049 compaction tiles: threads of the one-workgroup carry (1024) and of
+    the count scan (1024) each fold more than one tile, which no smaller case makes them do."""
+    n = 1024 * igx.engine.lw_join_tile() + 1
+    key, kind = R.random_stream(n, 5, seed=1)
+    take, b, live = _check(igx, key, kind)
+    assert len(take) > 100_000 and int((b != R.NONE).sum()) > 50_000 and len(live) >= 3
 
 
 def test_one_key_many_tiles(igx):
