@@ -494,7 +494,8 @@ int igx_groupby_sort(igx_table *t, const igx_tsortkey *keys, uint32_t nkeys, uin
  * are ranked), out2[1] = top-Ks answered by the full selection.  Both give the same slots. */
 int igx_groupby_topk_counts(igx_table *t, uint64_t *out2);
 int igx_groupby_destroy(igx_table *t);
-/* Diagnostics only (IGX_GB_DEBUG env), 32 words: out[0..1] LDS-cache hits / misses (bit 3);
+/* Diagnostics only (IGX_GB_DEBUG env), 32 words: out[0..1] LDS-cache hits / misses, out[2] the
+ * misses that found their set closed (bit 3);
  * out[4..7] sleep counts of loaders on a full miss ring, probers on an empty one, probers on a
  * full update ring, the idle server (bit 16); bit 18, the memory-side atomics: out[8..11] the
  * server wave's updates, of them minima, distinct (value record, opcode) pairs per instruction,

@@ -83,14 +83,22 @@ __device__ __forceinline__ void lds_tags(const LdsCache<KW> &c, uint32_t base, u
     tg[4] = t1.x; tg[5] = t1.y; tg[6] = t1.z; tg[7] = t1.w;
 }
 
+// `closed`: the set can never hold this key in this launch -- all 8 tags are set (a tag is set once
+// and entries are never evicted) and none is the key's.  A matching tag whose entry is not yet
+// published is an adoption in flight, possibly of this key: not closed.
 template <int KW>
-__device__ __forceinline__ int lds_lookup(const LdsCache<KW> &c, const uint32_t (&k)[KW], uint64_t h, uint32_t &gs) {
+__device__ __forceinline__ int lds_lookup(const LdsCache<KW> &c, const uint32_t (&k)[KW], uint64_t h, uint32_t &gs,
+                                          bool &closed) {
     const uint32_t base = lds_set(c, h), t = lds_tag(h);
     uint32_t tg[8];
     lds_tags(c, base, tg);
-    uint32_t m = 0;
+    uint32_t m = 0, open = 0;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) m |= (tg[j] == t ? 1u : 0u) << j;
+    for (int j = 0; j < 8; ++j) {
+        m |= (tg[j] == t ? 1u : 0u) << j;
+        open |= (tg[j] == 0 ? 1u : 0u);
+    }
+    closed = !m && !open;
     while (m) {   // usually zero or one candidate
         const uint32_t e = base + (uint32_t)(__builtin_ffs((int)m) - 1);
         m &= m - 1;
@@ -101,6 +109,12 @@ __device__ __forceinline__ int lds_lookup(const LdsCache<KW> &c, const uint32_t 
         }
     }
     return -1;
+}
+
+template <int KW>
+__device__ __forceinline__ int lds_lookup(const LdsCache<KW> &c, const uint32_t (&k)[KW], uint64_t h, uint32_t &gs) {
+    bool closed;
+    return lds_lookup<KW>(c, k, h, gs, closed);
 }
 
 // adopt a free entry of the key's set for a key just resolved in HBM
@@ -199,6 +213,9 @@ __device__ __forceinline__ void ring_push(const GbArgs &a, const Ring &r, uint32
 #pragma unroll
     for (int x = 0; x <= NA; ++x) {
         has[x] = x < NA ? (x < (int)a.naggs && v[x] != 0) : gidx < first_ins;
+#ifdef IGX_DIAG_NO_SUM_PUSH   // diagnostic build only (wrong sums): the bound of the logged sums' whole path
+        if (x < NA && a.log && (v[x < NA ? x : 0] >> 32) == 0 && gs < LOG_SLOT_LIMIT) has[x] = false;
+#endif
 #ifdef IGX_DIAG_HALF_ATOMICS   // diagnostic build only (wrong sums): the bound of one atomic per miss
         if (NA == 4 && (x == 1 || x == 3)) has[x] = false;
 #endif
@@ -386,6 +403,7 @@ __device__ __forceinline__ void ring_serve(const GbArgs &a, const Ring &r, uint3
 // producer of position p waits for seq == p, fills the cell and sets seq = p + 1; the
 // consumer of p waits for seq == p + 1, reads the cell and sets seq = p + MRING.
 constexpr uint32_t MRING = 256;
+constexpr uint32_t CELL_CLOSED = 1u << 31;   // in a cell's high index word: the key's LDS set is closed
 
 template <int KW, int NA>
 struct MissRing {
@@ -400,7 +418,7 @@ struct MissRing {
 
 template <int KW, int NA>
 __device__ __forceinline__ void miss_push(const MissRing<KW, NA> &m, const uint32_t (&k)[KW], uint64_t h,
-                                          uint64_t gidx, const uint64_t (&v)[NA]) {
+                                          uint64_t gidx, const uint64_t (&v)[NA], bool closed) {
     const uint64_t active = __ballot(true);
     const uint32_t leader = (uint32_t)__ffsll((long long)active) - 1;
     uint32_t base = 0;
@@ -419,7 +437,9 @@ __device__ __forceinline__ void miss_push(const MissRing<KW, NA> &m, const uint3
     for (int q = 0; q < MissRing<KW, NA>::KQ; ++q)
         cl[q] = make_uint4(4 * q + 0 < KW ? k[4 * q + 0] : 0u, 4 * q + 1 < KW ? k[4 * q + 1] : 0u,
                            4 * q + 2 < KW ? k[4 * q + 2] : 0u, 4 * q + 3 < KW ? k[4 * q + 3] : 0u);
-    cl[MissRing<KW, NA>::KQ] = make_uint4((uint32_t)h, (uint32_t)(h >> 32), (uint32_t)gidx, (uint32_t)(gidx >> 32));
+    // the loader's `closed` rides in the index word's top bit (indices stay below IDX_LIMIT = 2^48)
+    cl[MissRing<KW, NA>::KQ] = make_uint4((uint32_t)h, (uint32_t)(h >> 32), (uint32_t)gidx,
+                                          (uint32_t)(gidx >> 32) | (closed ? CELL_CLOSED : 0u));
 #pragma unroll
     for (int x = 0; x < NA; x += 2) {
         const uint64_t v1 = x + 1 < NA ? v[x + 1] : 0ull;
@@ -429,6 +449,10 @@ __device__ __forceinline__ void miss_push(const MissRing<KW, NA> &m, const uint3
     __hip_atomic_store(sq, p + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// A miss whose cell says `closed` skips the second lookup, the admission filter and the adoption
+// attempt (none can succeed: the set is full of other keys for the rest of the launch) and goes
+// straight to the probe and the update ring; either way its sums are added and its index is a
+// candidate minimum, so the result does not depend on the bit.
 // Probers resolve PB misses per lane at a time (PB = 1: two per lane measured slower -- C5
 // 6.41 -> 6.72-6.80 ms, C2 unchanged, and for the 72-B key they spill): the LDS cache again (a prober may have adopted the key since), then
 // the HBM table, then adoption of a free LDS entry or the HBM-update ring.
@@ -438,6 +462,7 @@ struct MissRow {
     uint32_t k[KW];
     uint64_t h, gidx;
     uint64_t v[NA];
+    uint32_t closed;   // non-zero: the loader saw the key's LDS set full of other keys (no lookup, no adoption)
 };
 
 template <int KW, int NA>
@@ -453,7 +478,11 @@ __device__ __forceinline__ void read_cell(const MissRing<KW, NA> &m, uint32_t p,
     }
     const uint4 hq = cl[MissRing<KW, NA>::KQ];
     x.h = (uint64_t)hq.x | ((uint64_t)hq.y << 32);
-    x.gidx = (uint64_t)hq.z | ((uint64_t)hq.w << 32);
+    x.gidx = (uint64_t)hq.z | ((uint64_t)(hq.w & ~CELL_CLOSED) << 32);
+    x.closed = hq.w & CELL_CLOSED;
+#ifdef IGX_DIAG_CLOSED_SKIP_ALL   // diagnostic build only: every miss skips the LDS work (nothing is adopted)
+    x.closed = CELL_CLOSED;
+#endif
 #pragma unroll
     for (int i = 0; i < NA; i += 2) {
         const uint4 t = cl[MissRing<KW, NA>::KQ + 1 + i / 2];
@@ -474,7 +503,7 @@ template <int KW, int NA, bool DBG>
 __device__ __forceinline__ void finish_miss(const GbArgs &a, const LdsCache<KW> &c, const Ring &r,
                                             const MissRow<KW, NA> &x, uint32_t gs, uint64_t first_ins,
                                             bool claimed = false) {
-    const int ad = ghost_admit<KW>(a, c, x.h) ? lds_adopt<KW>(c, x.k, x.h, gs) : -1;
+    const int ad = !x.closed && ghost_admit<KW>(a, c, x.h) ? lds_adopt<KW>(c, x.k, x.h, gs) : -1;
     if (claimed) return;   // the claim wrote this event's values into the new record
     if (ad >= 0) lds_accumulate<KW, NA>(a, c, ad, x.v, x.gidx);
     else ring_push<NA>(a, r, gs, x.v, x.gidx, first_ins);
@@ -542,7 +571,7 @@ __device__ __forceinline__ void prober_sm(const GbArgs &a, const LdsCache<KW> &c
                         read_cell<KW, NA>(m, p, x);
                         __hip_atomic_store(sq, p + MRING, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                         uint32_t gs = SLOT_OVF;
-                        const int slot = lds_lookup<KW>(c, x.k, x.h, gs);   // adopted meanwhile?
+                        const int slot = x.closed ? -1 : lds_lookup<KW>(c, x.k, x.h, gs);   // adopted meanwhile?
                         if (slot >= 0) {
                             lds_accumulate<KW, NA>(a, c, slot, x.v, x.gidx);
                         } else {
@@ -799,7 +828,7 @@ __device__ __forceinline__ void prober(const GbArgs &a, const LdsCache<KW> &c, c
             probes[j] = tries[j] = 0;
             if (have[j]) {
                 uint32_t g = SLOT_OVF;
-                const int slot = lds_lookup<KW>(c, x[j].k, x[j].h, g);
+                const int slot = x[j].closed ? -1 : lds_lookup<KW>(c, x[j].k, x[j].h, g);
                 if (slot >= 0) lds_accumulate<KW, NA>(a, c, slot, x[j].v, x[j].gidx);
                 else act[j] = true;
             }
@@ -891,7 +920,7 @@ __device__ __forceinline__ void prober(const GbArgs &a, const LdsCache<KW> &c, c
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
             if (gs[j] == SLOT_OVF) continue;
-            const int ad = ghost_admit<KW>(a, c, x[j].h) ? lds_adopt<KW>(c, x[j].k, x[j].h, gs[j]) : -1;
+            const int ad = !x[j].closed && ghost_admit<KW>(a, c, x[j].h) ? lds_adopt<KW>(c, x[j].k, x[j].h, gs[j]) : -1;
             if (claimed[j]) continue;   // a claim's values are in its new record already
             if (ad >= 0) lds_accumulate<KW, NA>(a, c, ad, x[j].v, x[j].gidx);
             else ring_push<NA>(a, r, gs[j], x[j].v, x[j].gidx, first_ins[j]);
@@ -1000,13 +1029,17 @@ __global__ __launch_bounds__(GTB) void k_groupby(GbArgs a) {
             }
             if (ok) {
                 uint32_t gs = SLOT_OVF;
-                const int slot = lds_lookup<KW>(c, k, h, gs);
-                if (DBG && (a.dbg & 8u)) atomicAdd(a.dbg_cnt + (slot >= 0 ? 0 : 1), 1ull);
+                bool closed;
+                const int slot = lds_lookup<KW>(c, k, h, gs, closed);
+                if (DBG && (a.dbg & 8u)) {
+                    atomicAdd(a.dbg_cnt + (slot >= 0 ? 0 : 1), 1ull);
+                    if (slot < 0 && closed) atomicAdd(a.dbg_cnt + 2, 1ull);   // of the misses: closed sets
+                }
                 if (slot >= 0) {
                     if (!(DBG && (a.dbg & 512u)))   // diagnostics: bit9 no LDS accumulate
                         lds_accumulate<KW, NA>(a, c, slot, v, row_gidx(a, row));
                 } else if (!(DBG && (a.dbg & 2u))) {
-                    miss_push<KW, NA>(m, k, h, row_gidx(a, row), v);
+                    miss_push<KW, NA>(m, k, h, row_gidx(a, row), v, closed);
                     ++nmiss;
                 }
             }

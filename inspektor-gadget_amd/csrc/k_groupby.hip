@@ -623,7 +623,9 @@ static int launch_form(igx_table *t, GbArgs &a) {
         if (const char *m = std::getenv("IGX_GB_SEED_MIN")) min_rows = std::strtoull(m, nullptr, 0);
         t->interval_seeded = false;
         // static key layouts only (the reference's BPF key structs)
-        if (!t->generic && t->seed_on && t->gen_planned && !a.dbg && a.n >= min_rows) {
+        // (a debug kernel runs unseeded, so that its ablations compare like with like -- except
+        // when it only counts, bit 3: then it counts what the production kernel would see)
+        if (!t->generic && t->seed_on && t->gen_planned && (!a.dbg || a.dbg == 8u) && a.n >= min_rows) {
             if (t->seed_left == 0 || !t->nseeds) {
                 uint32_t every = SEED_EVERY;
                 if (const char *e = std::getenv("IGX_GB_SEED_EVERY"))   // A/B knob
